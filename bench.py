@@ -14,6 +14,20 @@ train_dist.py:85), so global batch = 128*N.  Synthetic data, random-init
 weights (no network in this environment), fp32 (the reference's dtype).
 Timing: W untimed warmup steps, barrier+sync, exactly K timed steps,
 barrier+sync, MAX elapsed over ranks; rank 0 prints one JSON line.
+
+A plain run does only that.  --dump-outputs DIR saves, after the timed
+steps, what one more step through the timed path leaves its caller with
+(loss, parameters, gradients, momentum buffers) as DIR/<name>.npy,
+float32.  That step starts from the seeded initial weights, zero
+momentum and the initial dropout seed, because the trajectory itself is
+not comparable between runs: the kernels' floating-point atomics make
+two runs differ in the last bit after one step, and training amplifies
+that to 10% of a gradient by step 100 (measured on one MI355X).  From
+the restored state two runs, or two builds, agree to rounding, array
+for array.
+--full is where any measurement beyond the headline figure belongs
+(baselines, other configurations, per-kernel runs); the flagship has none
+today, so it currently adds nothing to a plain run.
 """
 
 import argparse
@@ -60,7 +74,67 @@ def parse_args():
                         "launch (measured slower than the 6-dispatch "
                         "fused path at B=128: the weight-gradient phase "
                         "loses workgroup parallelism — profiles/)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, run the timed step once "
+                        "more from the seeded initial state and save its "
+                        "loss, parameters, gradients and momentum "
+                        "buffers as DIR/<name>.npy (float32, rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that the "
+                        "headline figure does not need (none today)")
     return p.parse_args()
+
+
+# hard cap on what --dump-outputs may write
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_state(model, opt):
+    """Copy everything a step updates in place: weights, momentum
+    buffers, the device-side dropout seed and (CPU path) torch's RNG."""
+    return {
+        "params": [p.detach().clone() for p in model.parameters()],
+        "bufs": [b.clone() for b in opt._bufs or []],
+        "seeds": {k: v.clone() for k, v in ops._seed_bufs.items()},
+        "rng": torch.get_rng_state(),
+    }
+
+
+@torch.no_grad()
+def restore_state(model, opt, snap):
+    """Put a snapshot_state() back IN PLACE (a captured graph and the
+    flat gradient buffer keep pointing at the same memory)."""
+    for p, s in zip(model.parameters(), snap["params"]):
+        p.copy_(s)
+        if p.grad is not None:
+            p.grad.zero_()
+    for b, s in zip(opt._bufs or [], snap["bufs"]):
+        b.copy_(s)
+    for k, s in snap["seeds"].items():
+        ops._seed_bufs[k].copy_(s)
+    torch.set_rng_state(snap["rng"])
+
+
+def dump_outputs(dirpath, loss, model, opt):
+    """Save what a caller of the timed step is left with: the returned
+    loss and the state the step updated in place."""
+    import numpy as np
+    arrays = {"loss": loss}
+    names = [n for n, p in model.named_parameters() if p.requires_grad]
+    for n, p in model.named_parameters():
+        arrays["param." + n] = p
+        if p.grad is not None:
+            arrays["grad." + n] = p.grad
+    for n, buf in zip(names, opt._bufs or []):
+        arrays["momentum." + n] = buf
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs would write {total} bytes "
+                           f"(limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirpath, exist_ok=True)
+    for n, t in arrays.items():
+        np.save(os.path.join(dirpath, n + ".npy"),
+                t.detach().to("cpu", torch.float32).numpy())
 
 
 def main():
@@ -128,6 +202,12 @@ def main():
         use_mega = (args.megakernel and not args.graph and
                     args.batch <= 512 and net_step_available())
 
+    initial = None
+    if args.dump_outputs:
+        if not cpu_mode:
+            ops._seed_ptr(torch.device(device))  # create the seed buffer
+        initial = snapshot_state(model, opt)
+
     def step():
         if use_fused:
             if use_mega:
@@ -181,10 +261,11 @@ def main():
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            step()
+            graph_loss = step()
 
         def step():  # noqa: F811
             graph.replay()
+            return graph_loss
 
     for _ in range(args.warmup):
         step()
@@ -202,6 +283,14 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1000.0
     samples_per_sec = args.batch * world * args.steps / elapsed
+
+    if args.dump_outputs:
+        # every rank replays (the step holds collectives); rank 0 writes
+        restore_state(model, opt, initial)
+        loss = step()
+        barrier_sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, model, opt)
 
     if rank == 0:
         print(json.dumps({

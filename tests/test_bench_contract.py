@@ -103,3 +103,48 @@ def test_bench_single_process_json():
     d = json.loads([ln for ln in out.stdout.splitlines()
                     if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes, as float32 .npy files, the loss and the
+    updated state of one step through the timed path taken from the
+    seeded initial state, so the arrays depend on neither run nor step
+    count (bit for bit on CPU, where summation order is fixed).  --full
+    is accepted and leaves the result line's meaning alone."""
+    import numpy as np
+    env = dict(os.environ)
+    env["DTP_BENCH_CPU"] = "1"
+    results = []
+    for name, steps, extra in (("a", 2, []), ("b", 3, ["--full"])):
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps",
+             str(steps), "--warmup", "1", "--batch", "8", "--dump-outputs",
+             str(tmp_path / name), *extra],
+            cwd=ROOT, env=env, capture_output=True, text=True, timeout=180)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        results.append(json.loads(lines[0]))
+    for d, steps in zip(results, (2, 3)):
+        for k in REQUIRED:
+            assert k in d, k
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert d["metric"] == "ConvNet samples/sec"
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert "loss.npy" in files
+    for layer in ("conv1", "conv2", "fc1", "fc2"):
+        for kind in ("param", "grad", "momentum"):
+            assert f"{kind}.{layer}.weight.npy" in files
+            assert f"{kind}.{layer}.bias.npy" in files
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / "a" / f)
+        b = np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    # the dumped step really trained: its momentum buffer is the gradient
+    mom = np.load(tmp_path / "a" / "momentum.fc2.weight.npy")
+    assert np.abs(mom).max() > 0

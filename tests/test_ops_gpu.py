@@ -24,23 +24,29 @@ def _native_loaded():
     load_native("_kernels")
 
 
-def _cmp_fwd_bwd(fn_gpu, fn_ref, tensors, atol=1e-4, rtol=1e-4):
+def _cmp_fwd_bwd(fn_gpu, fn_ref, tensors, atol=1e-4, rtol=1e-4,
+                 ref_dtype=torch.float32):
+    """``ref_dtype=torch.float64`` evaluates the reference in double and
+    rounds it to fp32, so the tolerance is spent on the kernel's error
+    alone and not on the CPU reference's own fp32 summation order (which
+    changes with the host's thread count)."""
     gpu_in = [t.detach().to(DEV).requires_grad_(t.requires_grad)
               for t in tensors]
-    cpu_in = [t.detach().clone().requires_grad_(t.requires_grad)
-              for t in tensors]
+    cpu_in = [t.detach().to(ref_dtype, copy=True)
+              .requires_grad_(t.requires_grad) for t in tensors]
     out_g = fn_gpu(*gpu_in)
     out_c = fn_ref(*cpu_in)
-    assert torch.allclose(out_g.cpu(), out_c, atol=atol, rtol=rtol), \
-        (out_g.cpu() - out_c).abs().max()
-    gseed = torch.randn_like(out_c)
+    assert torch.allclose(out_g.cpu(), out_c.float(), atol=atol,
+                          rtol=rtol), \
+        (out_g.cpu() - out_c.float()).abs().max()
+    gseed = torch.randn_like(out_c, dtype=torch.float32)
     out_g.backward(gseed.to(DEV))
-    out_c.backward(gseed)
+    out_c.backward(gseed.to(ref_dtype))
     for a, b in zip(gpu_in, cpu_in):
         if a.requires_grad:
-            assert torch.allclose(a.grad.cpu(), b.grad, atol=atol,
+            assert torch.allclose(a.grad.cpu(), b.grad.float(), atol=atol,
                                   rtol=rtol), \
-                (a.grad.cpu() - b.grad).abs().max()
+                (a.grad.cpu() - b.grad.float()).abs().max()
 
 
 def test_conv2d_k1_shape():
@@ -63,13 +69,17 @@ def test_conv2d_k2_shape():
 
 
 def test_conv2d_large_batch():
+    # Each weight gradient sums 512*24*24 = 294912 products.  Torch's CPU
+    # fp32 conv2d backward is itself 4e-3 .. 4e-2 away from the exact sum
+    # there (more than atol, and varying with the thread count), while
+    # the kernel stays within 1.5e-3; so the reference is float64.
     torch.manual_seed(2)
     x = torch.randn(512, 1, 28, 28).requires_grad_(True)
     w = torch.randn(10, 1, 5, 5).requires_grad_(True)
     b = torch.randn(10).requires_grad_(True)
     _cmp_fwd_bwd(lambda x_, w_, b_: ops.conv2d(x_, w_, b_),
                  lambda x_, w_, b_: F.conv2d(x_, w_, b_), [x, w, b],
-                 atol=2e-3)
+                 atol=2e-3, ref_dtype=torch.float64)
 
 
 def test_maxpool_relu():
