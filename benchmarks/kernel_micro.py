@@ -22,7 +22,7 @@ from dist_tuto_pth_amd.ops.fused import _ws, attach_flat_grads  # noqa: E402
 from dist_tuto_pth_amd.utils.native import load_native  # noqa: E402
 
 # tile segment table — keep in sync with csrc/kernels.hip
-T_CONV2, T_FC1, T_CONV1, T_FC2 = 20, 63, 24, 2
+T_CONV2, T_FC1, T_CONV1, T_FC2 = 8, 63, 8, 2
 
 
 def time_fn(fn, reps=200, warmup=20):
@@ -90,17 +90,16 @@ def main():
     bwd()
     torch.cuda.synchronize()
 
-    # mirror csrc gw_nch()/gw_c1_subs() so raw segment launches match
+    # mirror csrc gw_nch()/gw_nch1()/gw_nch2() so raw segment launches match
     # what the fused step actually runs
-    nch = int(os.environ.get("DTP_GW_NCH", 0)) or         (16 if B <= 192 else (24 if B <= 768 else 32))
+    nch = int(os.environ.get("DTP_GW_NCH", 0)) or (16 if B <= 192 else 24)
     nch = min(nch, 32, B)
     bchunk = (B + nch - 1) // nch
     nch1 = min(int(os.environ.get("DTP_GW_NCH1", 0)) or nch, 32, B)
     bchunk1 = (B + nch1 - 1) // nch1
     nch2 = min(int(os.environ.get("DTP_GW_NCH2", 0)) or
-               (24 if B <= 192 else nch), 32, B)
+               (24 if B <= 192 else 32), 32, B)
     bchunk2 = (B + nch2 - 1) // nch2
-    c1_ext = (8 if bchunk <= 16 else 24) - 1
 
     def seg(base, ntiles):
         def f():
@@ -126,13 +125,13 @@ def main():
     results["gw all tiles"] = time_fn(seg(0, T_CONV2 + T_FC1 + T_CONV1 + T_FC2))
     results["gw combine"] = time_fn(lambda: k.net_gw_combine_raw(
         ws["part"].data_ptr(), [p.grad.data_ptr() for p in params], nch,
-        nch1, nch2, c1_ext, s))
+        nch1, nch2, s))
     ws.setdefault("loss_part", torch.empty(4096, device=dev))
     bufs = [b.data_ptr() for b in opt._bufs]
     results["gw combine+sgd+loss"] = time_fn(
         lambda: k.net_gw_combine_sgd_raw(
             ws["part"].data_ptr(), [p.grad.data_ptr() for p in params],
-            pp, bufs, nch, nch1, nch2, c1_ext, 0.01, 0.5,
+            pp, bufs, nch, nch1, nch2, 0.01, 0.5,
             ws["loss_part"].data_ptr(), ws["loss"].data_ptr(), 128, s))
     results["sgd"] = time_fn(opt.step)
 

@@ -1494,140 +1494,212 @@ net_fused_fwdbwd_kernel(
 #define OFF_BF1 21280     // 50
 #define OFF_WF2 21330     // 500
 #define OFF_BF2 21830     // 10
-#define T_CONV2 20        // conv2 tile columns (pair mode uses 10)
-static_assert(T_CONV2 == N_C2K, "conv2 gw tiling: one tile per output "
-              "channel (single mode) or per channel pair (pair mode)");
+#define T_CONV2 8         // conv2 tiles: 32-column slices of (c,r,s | bias)
 #define T_FC1 63          // ceil(16050/256)
-#define T_CONV1 24        // one sub-block per conv1 output row
+#define T_CONV1 8         // conv1 sub-blocks: bands of 3 output rows
 #define T_FC2 2           // ceil(510/256)
 #define GW_TILES (T_CONV2 + T_FC1 + T_CONV1 + T_FC2)
-// conv1's 24 sub-blocks write disjoint 260-float slices: sub 0 to the
-// canonical [OFF_W1,OFF_B1] region, subs 1-23 to an extension past
+// conv1's 8 sub-blocks write disjoint 260-float slices: sub 0 to the
+// canonical [OFF_W1,OFF_B1] region, subs 1-7 to an extension past
 // GW_TOTAL; the combine kernel folds the extension back in.
-#define GW_ROW (GW_TOTAL + 23 * 260)
+#define GW_ROW (GW_TOTAL + (T_CONV1 - 1) * 260)
 
-// conv2 weight-gradient fold, templated on channels-per-block so every
-// accumulator index is compile-time (a runtime nk spilled q[][] to
-// scratch and tripled the kernel — r2 ledger).  Thread = (ohGroup, c,
-// r), 200 lanes, owns all FIVE sx weights of its (c, r) row: one
-// 12-value xr window + one 8-value gr row feed 40 FMA per channel.
-// Staging is double-buffered float4.
-template <int NK, bool SC1 = false>
-__device__ __forceinline__ void net_gw_conv2_fold(
-    int k0, int tid, int b0, int b1, float* __restrict__ my,
+typedef float gw_f32x16 __attribute__((ext_vector_type(16)));
+typedef float gw_f32x4 __attribute__((ext_vector_type(4)));
+
+// conv2 weight gradient as an implicit GEMM on exact-fp32 MFMA
+// (v_mfma_f32_32x32x2_f32; numerics are a k-ordered fmaf chain):
+//   M = 20 output channels (rows 20..31 fed zeros),
+//   N = 250 (c,r,s) columns + the bias as column 250 (B = ones),
+//       cut into 8 tiles of 32 — ONE BLOCK PER COLUMN TILE, all 20
+//       channels, so a chunk row stages p1 8 x (<= 3 of 10 planes)
+//       instead of 10-20 x the whole plane,
+//   K = (b, oh, ow), 64 per sample, split over the 4 waves: wave w owns
+//       positions 16w..16w+15.  K order inside a wave is free as long as
+//       A and B agree, so MFMA step j (0..7) of lane half h is position
+//       16w + 8h + j, i.e. (oh, ow) = (2w + h, j): the A operand is 8
+//       CONTIGUOUS ga2 floats per lane (two float4 loads straight from
+//       global, prefetched one sample ahead) and the B operand 8
+//       contiguous LDS floats at a per-lane column base.
+// Operand lane map (32x32x2): lane l gives A[row l&31][k l>>5] and
+// B[k l>>5][col l&31]; D[row (reg&3) + 8*(reg>>2) + 4*(l>>5)][col l&31].
+// One accumulator tile per wave is enough: the 32x32x2 dependent-chain
+// latency equals its issue interval (64 clk).  The four K-slices are
+// summed once per chunk through LDS in a fixed order (deterministic).
+// Every accumulator index is compile-time (a runtime index spilled to
+// scratch and tripled this kernel once — r2 ledger).
+static_assert(T_CONV2 * 32 >= 251, "conv2 gw column tiles cover 250 + bias");
+template <bool SC1 = false>
+__device__ __forceinline__ void net_gw_conv2_mfma(
+    int nt, int tid, int b0, int b1, float* __restrict__ my,
     const float* __restrict__ p1_ws, const float* __restrict__ ga2_ws) {
-  // statics INSIDE the template: the two instantiations each get an
-  // allocation (the kernel carries both), but a caller-hoisted shared
-  // buffer passed as pointers measured 15% SLOWER end to end (730 vs
-  // 631 us gw-all at B=4096, same box) — the pointer indirection costs
-  // more than the duplicated LDS at this occupancy (r2 A/B, ledger).
-  __shared__ __attribute__((aligned(16))) float sp1[2][N_P1];
-  __shared__ __attribute__((aligned(16))) float sg2[2][64 * NK];
-  __shared__ float wacc[NK][251];
-  const int ohp = tid / 50;          // 0..3 (tid < 200)
-  const int cr = tid % 50;
-  const int c = cr / 5, r = cr % 5;
-  float q[NK][5] = {};
-  float be[NK] = {}, bo[NK] = {};
-  for (int i = tid; i < NK * 251; i += 256) wacc[i / 251][i % 251] = 0.f;
-  // prologue: stage b0 into buffer 0 (sp1 rows and the per-sample
-  // bases are 16 B aligned).  b0 < b1 guard: ceil-rounded chunk counts
-  // leave EMPTY tail rows for non-divisible B (e.g. B=100, nch=16,
-  // bchunk=7 -> row 15 starts at sample 105) — staging unconditionally
-  // read up to ~6 KB past p1_ws/ga2_ws for those rows; the zeroed wacc
-  // flush below is all an empty row needs.
+  __shared__ __attribute__((aligned(16))) float sp1[2][3 * 144];
+  __shared__ float red[4][N_C2K * 32];
+  const int lane = tid & 63, w = tid >> 6;
+  const int col = lane & 31, h = lane >> 5;
+  const int n = nt * 32 + col;
+  // 32 consecutive columns touch at most 3 input channels
+  const int c_lo = (nt * 32) / 25;
+  const int c_hi = min(N_C1K - 1, (nt * 32 + 31) / 25);
+  const int nst4 = (c_hi - c_lo + 1) * 36;  // float4s to stage (<= 108)
+  // per-lane im2col base: c*144 + (oh + r)*12 + (ow + s), oh = 2w + h
+  int base = (2 * w + h) * 12;
+  if (n < 250) base += (n / 25 - c_lo) * 144 + ((n % 25) / 5) * 12 + n % 5;
+  const float bfix = (n == 250) ? 1.f : 0.f;  // bias column / padding
+  const int aoff = col * 64 + 16 * w + 8 * h;
+  gw_f32x16 acc;
+  #pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+  // b0 < b1 guard: ceil-rounded chunk counts leave EMPTY tail rows for
+  // non-divisible B (e.g. B=100, nch=16, bchunk=7 -> row 15 starts at
+  // sample 105); such a row must touch no memory and flush zeros.
   if (b0 < b1) {
-    float4* d4 = reinterpret_cast<float4*>(sp1[0]);
-    const float4* s4 = reinterpret_cast<const float4*>(
-        p1_ws + (int64_t)b0 * N_P1);
-    for (int i = tid; i < N_P1 / 4; i += 256) d4[i] = s4[i];
-    float4* g4 = reinterpret_cast<float4*>(sg2[0]);
-    const float4* a4 = reinterpret_cast<const float4*>(
-        ga2_ws + (int64_t)b0 * N_A2 + k0 * 64);
-    if (tid < 16 * NK) g4[tid] = a4[tid];
+    if (tid < nst4)
+      reinterpret_cast<float4*>(sp1[0])[tid] =
+          reinterpret_cast<const float4*>(
+              p1_ws + (int64_t)b0 * N_P1 + c_lo * 144)[tid];
+    if (col < N_C2K) {
+      const float4* ap = reinterpret_cast<const float4*>(
+          ga2_ws + (int64_t)b0 * N_A2 + aoff);
+      a0 = ap[0];
+      a1 = ap[1];
+    }
   }
   __syncthreads();
   for (int b = b0; b < b1; ++b) {
     const int cur = (b - b0) & 1;
-    if (b + 1 < b1) {  // stage next sample into the other buffer
-      float4* d4 = reinterpret_cast<float4*>(sp1[cur ^ 1]);
-      const float4* s4 = reinterpret_cast<const float4*>(
-          p1_ws + (int64_t)(b + 1) * N_P1);
-      for (int i = tid; i < N_P1 / 4; i += 256) d4[i] = s4[i];
-      float4* g4 = reinterpret_cast<float4*>(sg2[cur ^ 1]);
-      const float4* a4 = reinterpret_cast<const float4*>(
-          ga2_ws + (int64_t)(b + 1) * N_A2 + k0 * 64);
-      if (tid < 16 * NK) g4[tid] = a4[tid];
-    }
-    if (tid < 200) {
-      #pragma unroll
-      for (int ohh = 0; ohh < 2; ++ohh) {
-        const int oh = ohp * 2 + ohh;
-        const float* xr = sp1[cur] + c * 144 + (r + oh) * 12;
-        float xv[12];
-        #pragma unroll
-        for (int j = 0; j < 12; ++j) xv[j] = xr[j];
-        #pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-          const float* gr = sg2[cur] + kk * 64 + oh * 8;
-          #pragma unroll
-          for (int ow = 0; ow < 8; ++ow) {
-            const float g = gr[ow];
-            q[kk][0] += g * xv[ow];
-            q[kk][1] += g * xv[ow + 1];
-            q[kk][2] += g * xv[ow + 2];
-            q[kk][3] += g * xv[ow + 3];
-            q[kk][4] += g * xv[ow + 4];
-          }
-        }
-      }
-    } else if (tid == 200) {  // biases: two chains per channel
-      #pragma unroll
-      for (int kk = 0; kk < NK; ++kk) {
-        const float* sg = sg2[cur] + kk * 64;
-        #pragma unroll
-        for (int j = 0; j < 64; j += 2) {
-          be[kk] += sg[j];
-          bo[kk] += sg[j + 1];
-        }
+    // next sample: global loads issued before the MFMAs, LDS write after
+    const bool more = b + 1 < b1;
+    float4 st = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 n0 = st, n1 = st;
+    if (more) {
+      if (tid < nst4)
+        st = reinterpret_cast<const float4*>(
+            p1_ws + (int64_t)(b + 1) * N_P1 + c_lo * 144)[tid];
+      if (col < N_C2K) {
+        const float4* ap = reinterpret_cast<const float4*>(
+            ga2_ws + (int64_t)(b + 1) * N_A2 + aoff);
+        n0 = ap[0];
+        n1 = ap[1];
       }
     }
+    const float* bp = sp1[cur] + base;
+    float bv[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) bv[j] = (n < 250) ? bp[j] : bfix;
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, bv[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, bv[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, bv[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, bv[3], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, bv[4], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, bv[5], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, bv[6], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, bv[7], acc, 0, 0, 0);
+    if (more && tid < nst4)
+      reinterpret_cast<float4*>(sp1[cur ^ 1])[tid] = st;
+    a0 = n0;
+    a1 = n1;
     __syncthreads();
   }
-  if (tid < 200) {
-    const int e = c * 25 + r * 5;
-    #pragma unroll
-    for (int kk = 0; kk < NK; ++kk) {
-      atomicAdd(&wacc[kk][e + 0], q[kk][0]);
-      atomicAdd(&wacc[kk][e + 1], q[kk][1]);
-      atomicAdd(&wacc[kk][e + 2], q[kk][2]);
-      atomicAdd(&wacc[kk][e + 3], q[kk][3]);
-      atomicAdd(&wacc[kk][e + 4], q[kk][4]);
-    }
-  } else if (tid == 200) {
-    #pragma unroll
-    for (int kk = 0; kk < NK; ++kk) wacc[kk][250] = be[kk] + bo[kk];
+  // rows (channels) 0..19 of this wave's K-slice -> red[w][k][col]
+  #pragma unroll
+  for (int reg = 0; reg < 12; ++reg) {
+    const int k = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    if (reg < 8 || h == 0) red[w][k * 32 + col] = acc[reg];
   }
   __syncthreads();
-  if (tid < 250) {
-    #pragma unroll
-    for (int kk = 0; kk < NK; ++kk)
-      gw_st<SC1>(my + OFF_W2 + (k0 + kk) * 250 + tid, wacc[kk][tid]);
-  }
-  if (tid == 250) {
-    #pragma unroll
-    for (int kk = 0; kk < NK; ++kk)
-      gw_st<SC1>(my + OFF_B2 + k0 + kk, wacc[kk][250]);
+  for (int i = tid; i < N_C2K * 32; i += 256) {
+    const int k = i >> 5, nn = nt * 32 + (i & 31);
+    const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    if (nn < 250)
+      gw_st<SC1>(my + OFF_W2 + k * 250 + nn, v);
+    else if (nn == 250)
+      gw_st<SC1>(my + OFF_B2 + k, v);
   }
 }
 
+// conv1 weight gradient on exact-fp32 MFMA (v_mfma_f32_16x16x4_f32):
+//   M = 10 output channels (pad 16), N = 25 (r,s) + the bias as column
+//   25 (B = ones), pad 32 = two 16-wide tiles sharing the A operand,
+//   K = (b, oh, ow).  Sub-block `sub` of T_CONV1 owns a band of
+//   24/T_CONV1 output rows; inside it the (sample, row) pairs are dealt
+//   round-robin to the 4 waves.  One row = 24 positions = 6 MFMA steps:
+//   step j of lane group q = l>>4 is ow = 6q + j, so each lane reads 6
+//   contiguous ga1 floats (A) and 6 contiguous x floats per tile (B)
+//   straight from global — these re-reads are L1 hits (r2 ledger), and
+//   there is no barrier in the K loop.
+// Lane map (16x16x4): A[row l&15][k l>>4], B[k l>>4][col l&15];
+// D[row 4*(l>>4) + reg][col l&15].  Two independent accumulator tiles
+// per wave cover the 40-clk dependent latency (32-clk issue).
+template <bool SC1 = false>
+__device__ __forceinline__ void net_gw_conv1_mfma(
+    int sub, int tid, int b0, int b1, float* __restrict__ my,
+    const float* __restrict__ x, const float* __restrict__ ga1_ws) {
+  __shared__ float red[4][260];
+  const int lane = tid & 63, w = tid >> 6;
+  const int m = lane & 15, q = lane >> 4;
+  constexpr int rows = 24 / T_CONV1;
+  static_assert(rows * T_CONV1 == 24, "conv1 bands tile the 24 rows");
+  const int oh0 = sub * rows;
+  const int n1 = 16 + m;  // second tile: 16..24 weights, 25 bias, 26.. pad
+  const int xo0 = (m / 5) * 28 + m % 5 + 6 * q;
+  const int xo1 = (n1 < 25) ? (n1 / 5) * 28 + n1 % 5 + 6 * q : 0;
+  const float bfix = (n1 == 25) ? 1.f : 0.f;
+  const int ao = m * 576 + 6 * q;
+  gw_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  const int ntask = (b1 > b0) ? (b1 - b0) * rows : 0;
+  for (int t = w; t < ntask; t += 4) {
+    const int bb = t / rows;
+    const int b = b0 + bb, oh = oh0 + (t - bb * rows);
+    float av[6], v0[6], v1[6];
+    if (m < N_C1K) {
+      const float2* gp = reinterpret_cast<const float2*>(
+          ga1_ws + (int64_t)b * N_A1 + ao + oh * 24);
+      const float2 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+      av[0] = g0.x; av[1] = g0.y; av[2] = g1.x;
+      av[3] = g1.y; av[4] = g2.x; av[5] = g2.y;
+    } else {
+      #pragma unroll
+      for (int j = 0; j < 6; ++j) av[j] = 0.f;
+    }
+    const float* xp = x + (int64_t)b * 784 + oh * 28;
+    #pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      v0[j] = xp[xo0 + j];
+      v1[j] = (n1 < 25) ? xp[xo1 + j] : bfix;
+    }
+    #pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], v0[j], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], v1[j], acc1, 0, 0, 0);
+    }
+  }
+  #pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int k = 4 * q + reg;
+    if (k < N_C1K) {
+      red[w][k * 25 + m] = acc0[reg];
+      if (n1 < 25) red[w][k * 25 + n1] = acc1[reg];
+      if (n1 == 25) red[w][250 + k] = acc1[reg];
+    }
+  }
+  __syncthreads();
+  // sub 0 writes the canonical region, subs 1.. the extension rows
+  float* dst = (sub == 0) ? (my + OFF_W1)
+                          : (my + GW_TOTAL + (sub - 1) * 260);
+  for (int i = tid; i < 260; i += 256)
+    gw_st<SC1>(dst + i,
+               (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+}
+
 // One (tile, batch-chunk) partial weight-gradient reduction.  Tiles
-// walk [conv2 | fc1 | conv1x4 | fc2]; partials land in my[GW_ROW]
+// walk [conv2 x8 | conv1 x8 | fc1 | fc2]; partials land in my[GW_ROW]
 // laid out like the flat grad buffer.  Shared by net_gw_partial_kernel
 // and the single-launch net_step_kernel.
 template <bool SC1 = false>
 __device__ __forceinline__ void net_gw_tile(
-    int tile, int tid, int b0, int b1, int c1_subs,
+    int tile, int tid, int b0, int b1,
     float* __restrict__ my,
     const float* __restrict__ x,
     const float* __restrict__ p1_ws,
@@ -1638,82 +1710,17 @@ __device__ __forceinline__ void net_gw_tile(
     const float* __restrict__ gh1_ws,
     const float* __restrict__ glog_ws) {
   if (tile < T_CONV2) {  // conv2: gw [20][10][5][5] + gb [20]
-    // TWO block shapes, chosen by chunk size (measured, r2 ledger):
-    //  * pair mode (bchunk <= 16, i.e. B <= 512): one block folds TWO
-    //    output channels from one staging of the p1 plane — halves
-    //    the dominant HBM re-read; tiles 10..19 idle (the grid is
-    //    launch-granularity-bound here, idle blocks are free).
-    //  * single mode (large B): one channel per block — smaller
-    //    blocks pack the 2600-block grid without straggler tails,
-    //    which beats the re-read saving end to end.
-    if (b1 - b0 <= 16) {
-      if (tile < N_C2K / 2)
-        net_gw_conv2_fold<2, SC1>(tile * 2, tid, b0, b1, my, p1_ws,
-                                  ga2_ws);
-    } else {
-      net_gw_conv2_fold<1, SC1>(tile, tid, b0, b1, my, p1_ws, ga2_ws);
-    }
+    // one code path for every chunk size: a block is one 32-column
+    // slice of the implicit GEMM over ALL 20 output channels
+    net_gw_conv2_mfma<SC1>(tile, tid, b0, b1, my, p1_ws, ga2_ws);
     return;
   }
   tile -= T_CONV2;
   if (tile < T_CONV1) {  // conv1: gw [10][1][5][5] + gb [10]
-    // 250 outputs is too little parallelism for element-per-thread at
-    // this cost (24x24 window x batch): split each output over its 24
-    // output rows, LDS-atomic reduce.  The sub-block count is
-    // ADAPTIVE (r2): 24 single-row subs at large B (this family was
-    // the gw straggler: 3x the blocks, 281 -> 254 us at B=4096) but 8
-    // three-row bands at small B, where the extra 16 extension rows
-    // made the COMBINE 3x slower (8 -> 24 us) for nothing.  Sub 0
-    // writes the canonical region, subs 1..c1_subs-1 the extension
-    // rows; the combine folds c1_subs-1 rows.
-    // (r2 note: an LDS-staged double-buffered variant was MEASURED
-    // SLOWER — the grow/x re-reads are L1 hits and the staging math
-    // cost more than it saved.)
-    const int sub = tile;
-    if (sub >= c1_subs) return;
-    const int rows = 24 / c1_subs;     // 3 (band mode) or 1 (row mode)
-    const int oh0 = sub * rows;
-    const int n_w = 250 * rows;
-    __shared__ float wacc[260];
-    for (int i = tid; i < 260; i += 256) wacc[i] = 0.f;
-    __syncthreads();
-    for (int it = tid; it < n_w + 10 * rows; it += 256) {
-      float a = 0.f;
-      if (it < n_w) {
-        const int e = it / rows, oh = oh0 + it % rows;
-        const int k = e / 25, r = (e / 5) % 5, sx = e % 5;
-        // unroll 2: each sample's rows are a cold HBM first-touch for
-        // this block; interleaving two iterations overlaps the load
-        // latency the serial accumulate chain was exposing (r2)
-        #pragma unroll 2
-        for (int b = b0; b < b1; ++b) {
-          const float* grow = ga1_ws + (int64_t)b * N_A1 + k * 576 +
-                              oh * 24;
-          const float* xrow = x + (int64_t)b * 784 + (oh + r) * 28 + sx;
-          float ae = 0.f, ao = 0.f;
-          #pragma unroll
-          for (int ow = 0; ow < 24; ow += 2) {
-            ae += grow[ow] * xrow[ow];
-            ao += grow[ow + 1] * xrow[ow + 1];
-          }
-          a += ae + ao;
-        }
-        atomicAdd(&wacc[e], a);
-      } else {
-        const int j = it - n_w;
-        const int k = j / rows, oh = oh0 + j % rows;
-        for (int b = b0; b < b1; ++b) {
-          const float* grow = ga1_ws + (int64_t)b * N_A1 + k * 576 +
-                              oh * 24;
-          #pragma unroll 8
-          for (int ow = 0; ow < 24; ++ow) a += grow[ow];
-        }
-        atomicAdd(&wacc[250 + k], a);
-      }
-    }
-    __syncthreads();
-    float* dst = (sub == 0) ? (my + OFF_W1) : (my + GW_TOTAL + (sub - 1) * 260);
-    for (int i = tid; i < 260; i += 256) gw_st<SC1>(dst + i, wacc[i]);
+    // K (the 24 output rows x batch chunk) is split over T_CONV1
+    // sub-blocks; sub 0 writes the canonical region, subs 1.. the
+    // extension rows, which the combine folds.
+    net_gw_conv1_mfma<SC1>(tile, tid, b0, b1, my, x, ga1_ws);
     return;
   }
   tile -= T_CONV1;
@@ -1767,7 +1774,7 @@ __device__ __forceinline__ void net_gw_tile(
 }
 
 __global__ void __launch_bounds__(256)
-net_gw_partial_kernel(int c1_subs, const float* __restrict__ x,
+net_gw_partial_kernel(const float* __restrict__ x,
                       const float* __restrict__ p1_ws,
                       const float* __restrict__ p2_ws,
                       const float* __restrict__ d3_ws,
@@ -1788,7 +1795,7 @@ net_gw_partial_kernel(int c1_subs, const float* __restrict__ x,
   if ((int)blockIdx.y >= (c2 ? nch2 : c1 ? nch1 : nch)) return;
   const int bc = c2 ? bchunk2 : c1 ? bchunk1 : bchunk;
   net_gw_tile(tile, threadIdx.x, (int)blockIdx.y * bc,
-              min(B, ((int)blockIdx.y + 1) * bc), c1_subs,
+              min(B, ((int)blockIdx.y + 1) * bc),
               part + (int64_t)blockIdx.y * GW_ROW,
               x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws, glog_ws);
 }
@@ -1799,7 +1806,7 @@ struct GwPtrs { float* p[8]; };
 // sum flat-grad element i over the nch chunk rows (+ conv1 extension)
 template <bool SC1 = false>
 __device__ __forceinline__ float net_gw_combine_elem(
-    int i, int nch, int nch1, int nch2, int c1_ext,
+    int i, int nch, int nch1, int nch2,
     const float* __restrict__ part) {
   // four independent accumulator chains: the single 32-deep
   // load+add chain was latency-bound (VALUBusy ~0, profiles/).
@@ -1821,29 +1828,15 @@ __device__ __forceinline__ float net_gw_combine_elem(
   }
   for (; c < n; ++c) a0 += gw_ld<SC1>(part + (int64_t)c * GW_ROW + i);
   if (i < 260) {  // conv1 sub-block extension rows (see GW_ROW)
-    // c1_ext is 7 (band mode) or 23 (row mode): branch to fully
-    // unrolled folds — a runtime-bound loop here cost the combine
-    // 50% (8.1 -> 12.2 us, r2 ledger)
-    if (c1_ext == 7) {
-      for (int c2 = 0; c2 < nch1; ++c2) {
-        const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-        a0 += gw_ld<SC1>(ext + i) + gw_ld<SC1>(ext + 4 * 260 + i);
-        a1 += gw_ld<SC1>(ext + 260 + i) + gw_ld<SC1>(ext + 5 * 260 + i);
-        a2 += gw_ld<SC1>(ext + 2 * 260 + i) +
-              gw_ld<SC1>(ext + 6 * 260 + i);
-        a3 += gw_ld<SC1>(ext + 3 * 260 + i);
-      }
-    } else {
-      for (int c2 = 0; c2 < nch1; ++c2) {
-        const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-        #pragma unroll
-        for (int s = 0; s < 23; s += 4) {
-          a0 += gw_ld<SC1>(ext + s * 260 + i);
-          if (s + 1 < 23) a1 += gw_ld<SC1>(ext + (s + 1) * 260 + i);
-          if (s + 2 < 23) a2 += gw_ld<SC1>(ext + (s + 2) * 260 + i);
-          if (s + 3 < 23) a3 += gw_ld<SC1>(ext + (s + 3) * 260 + i);
-        }
-      }
+    // fully unrolled over the 7 rows — a runtime-bound loop here cost
+    // the combine 50% (8.1 -> 12.2 us, r2 ledger)
+    static_assert(T_CONV1 == 8, "extension fold is unrolled for 7 rows");
+    for (int c2 = 0; c2 < nch1; ++c2) {
+      const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
+      a0 += gw_ld<SC1>(ext + i) + gw_ld<SC1>(ext + 4 * 260 + i);
+      a1 += gw_ld<SC1>(ext + 260 + i) + gw_ld<SC1>(ext + 5 * 260 + i);
+      a2 += gw_ld<SC1>(ext + 2 * 260 + i) + gw_ld<SC1>(ext + 6 * 260 + i);
+      a3 += gw_ld<SC1>(ext + 3 * 260 + i);
     }
   }
   return (a0 + a1) + (a2 + a3);
@@ -1856,7 +1849,7 @@ __device__ __forceinline__ float net_gw_combine_elem(
 // ran a latency-exposed 8-deep L2 chain (profiles/).  Returns the full
 // sum on EVERY lane of the quad (butterfly reduction).
 __device__ __forceinline__ float net_gw_combine_elem_quad(
-    int i, int q, int nch, int nch1, int nch2, int c1_ext,
+    int i, int q, int nch, int nch1, int nch2,
     const float* __restrict__ part) {
   const int n = i < 260 ? nch1
               : (i >= OFF_W2 && i < OFF_WF1) ? nch2 : nch;
@@ -1866,24 +1859,12 @@ __device__ __forceinline__ float net_gw_combine_elem_quad(
   for (int c = q + 4; c < n; c += 8)
     a1 += part[(int64_t)c * GW_ROW + i];
   if (i < 260) {  // conv1 extension rows, spread across the quad
-    // fully unrolled per mode (see net_gw_combine_elem note)
-    if (c1_ext == 7) {
-      if (q == 0) {
-        for (int c2 = 0; c2 < nch1; ++c2) {
-          const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-          a0 += ext[i] + ext[260 + i] + ext[2 * 260 + i] +
-                ext[3 * 260 + i];
-          a1 += ext[4 * 260 + i] + ext[5 * 260 + i] + ext[6 * 260 + i];
-        }
-      }
-    } else {
+    // fully unrolled (see net_gw_combine_elem note)
+    if (q == 0) {
       for (int c2 = 0; c2 < nch1; ++c2) {
         const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-        #pragma unroll
-        for (int s = 0; s < 23; s += 8) {
-          if (s + q < 23) a0 += ext[(s + q) * 260 + i];
-          if (s + q + 4 < 23) a1 += ext[(s + q + 4) * 260 + i];
-        }
+        a0 += ext[i] + ext[260 + i] + ext[2 * 260 + i] + ext[3 * 260 + i];
+        a1 += ext[4 * 260 + i] + ext[5 * 260 + i] + ext[6 * 260 + i];
       }
     }
   }
@@ -1927,7 +1908,7 @@ __device__ __forceinline__ void net_loss_finalize(
 
 __global__ void net_gw_combine_kernel(const float* __restrict__ part,
                                       GwPtrs g, int nch, int nch1,
-                                      int nch2, int c1_ext,
+                                      int nch2,
                                       const float* __restrict__ loss_part,
                                       float* __restrict__ loss_out,
                                       int nblk_fwd,
@@ -1939,7 +1920,7 @@ __global__ void net_gw_combine_kernel(const float* __restrict__ part,
        t4 += (int64_t)gridDim.x * blockDim.x) {
     const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
     const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               c1_ext, part);
+                                               part);
     if (q == 0) {
       const int t = net_gw_tensor_of(i, off);
       g.p[t][i - off[t]] = acc;
@@ -1957,7 +1938,7 @@ __global__ void net_gw_combine_kernel(const float* __restrict__ part,
 __global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
                                           GwPtrs g, GwPtrs prm,
                                           GwPtrs buf, int nch, int nch1,
-                                          int nch2, int c1_ext,
+                                          int nch2,
                                           float lr,
                                           float mu,
                                           const float* __restrict__ loss_part,
@@ -1971,7 +1952,7 @@ __global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
        t4 += (int64_t)gridDim.x * blockDim.x) {
     const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
     const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               c1_ext, part);
+                                               part);
     if (q == 0) {
       const int t = net_gw_tensor_of(i, off);
       const int64_t j = i - off[t];
@@ -2000,8 +1981,8 @@ __global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
 // reads every row with plain loads.  Fold regions are per COLUMN (what the
 // column's own blocks wrote), so counter==target implies the region's rows
 // are all visible:
-//   conv2 column k  -> channel k (pair mode: column k<10 -> channels 2k,
-//                      2k+1; columns 10..19 wrote nothing and own nothing)
+//   conv2 column t  -> columns 32t..32t+31 of (c,r,s | bias), all 20
+//                      output channels
 //   conv1 family    -> ONE counter over all T_CONV1*nch blocks (its
 //                      sub-blocks share the 260 outputs via extension rows,
 //                      so no single column's completion suffices)
@@ -2009,32 +1990,37 @@ __global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
 // Each fold runs as soon as ITS column's blocks are done — overlapped with
 // the other families still computing — so the only exposed cost is the
 // straggler family's own (tiny) fold.
-__device__ __forceinline__ void net_gw_fold_range(
-    int i0, int i1, int nch, int c1_ext, const float* __restrict__ part,
+__device__ __forceinline__ void net_gw_fold_one(
+    int i, int nch, const float* __restrict__ part,
     const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
     float mu, bool do_sgd) {
   const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
                       OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
-    const float acc = net_gw_combine_elem<true>(i, nch, nch, nch,
-                                                c1_ext, part);
-    const int t = net_gw_tensor_of(i, off);
-    const int64_t j = i - off[t];
-    g.p[t][j] = acc;
-    if (do_sgd) {
-      float v = acc;
-      if (buf.p[t]) {
-        v = mu * buf.p[t][j] + acc;
-        buf.p[t][j] = v;
-      }
-      prm.p[t][j] -= lr * v;
+  const float acc = net_gw_combine_elem<true>(i, nch, nch, nch, part);
+  const int t = net_gw_tensor_of(i, off);
+  const int64_t j = i - off[t];
+  g.p[t][j] = acc;
+  if (do_sgd) {
+    float v = acc;
+    if (buf.p[t]) {
+      v = mu * buf.p[t][j] + acc;
+      buf.p[t][j] = v;
     }
+    prm.p[t][j] -= lr * v;
   }
+}
+
+__device__ __forceinline__ void net_gw_fold_range(
+    int i0, int i1, int nch, const float* __restrict__ part,
+    const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
+    float mu, bool do_sgd) {
+  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256)
+    net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, do_sgd);
 }
 
 template <bool DO_SGD>
 __global__ void __launch_bounds__(256)
-net_gw_partial_fold_kernel(int c1_subs, const float* __restrict__ x,
+net_gw_partial_fold_kernel(const float* __restrict__ x,
                            const float* __restrict__ p1_ws,
                            const float* __restrict__ p2_ws,
                            const float* __restrict__ d3_ws,
@@ -2050,7 +2036,7 @@ net_gw_partial_fold_kernel(int c1_subs, const float* __restrict__ x,
                            unsigned int* __restrict__ cnt) {
   const int b0 = blockIdx.y * bchunk;
   net_gw_tile<true>(blockIdx.x, threadIdx.x, b0, min(B, b0 + bchunk),
-                    c1_subs, part + (int64_t)blockIdx.y * GW_ROW,
+                    part + (int64_t)blockIdx.y * GW_ROW,
                     x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws,
                     glog_ws);
   // ---- last-arriver ticket, FENCE-FREE: the tile wrote its partials
@@ -2077,38 +2063,29 @@ net_gw_partial_fold_kernel(int c1_subs, const float* __restrict__ x,
     __hip_atomic_store(&cnt[ci], 0u, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);  // re-arm for next step
   __syncthreads();
-  const int c1_ext = c1_subs - 1;
-  if (xcol < T_CONV2) {  // conv2: this column's channel(s)
-    int k0, nk;
-    if (bchunk <= 16) {  // pair mode (mirrors net_gw_tile's split)
-      if (xcol >= N_C2K / 2) return;  // idle pair columns wrote nothing
-      k0 = xcol * 2;
-      nk = 2;
-    } else {
-      k0 = xcol;
-      nk = 1;
+  if (xcol < T_CONV2) {  // conv2: this column's 32-wide slice, all k
+    for (int e = (int)threadIdx.x; e < N_C2K * 32; e += 256) {
+      const int k = e >> 5, nn = xcol * 32 + (e & 31);
+      if (nn > 250) continue;
+      const int i = nn < 250 ? OFF_W2 + k * 250 + nn : OFF_B2 + k;
+      net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, DO_SGD);
     }
-    net_gw_fold_range(OFF_W2 + k0 * 250, OFF_W2 + (k0 + nk) * 250, nch,
-                      c1_ext, part, g, prm, buf, lr, mu, DO_SGD);
-    net_gw_fold_range(OFF_B2 + k0, OFF_B2 + k0 + nk, nch, c1_ext, part,
-                      g, prm, buf, lr, mu, DO_SGD);
     return;
   }
-  if (conv1_fam) {  // conv1: canonical 260 + extension rows (c1_ext)
-    net_gw_fold_range(0, 260, nch, c1_ext, part, g, prm, buf, lr, mu,
+  if (conv1_fam) {  // conv1: canonical 260 + extension rows
+    net_gw_fold_range(0, 260, nch, part, g, prm, buf, lr, mu,
                       DO_SGD);
     return;
   }
   if (xcol < T_CONV2 + T_CONV1 + T_FC1) {  // fc1 column slice
     const int i0 = OFF_WF1 + (xcol - (T_CONV2 + T_CONV1)) * 256;
-    net_gw_fold_range(i0, min(OFF_WF1 + 16050, i0 + 256), nch, c1_ext,
-                      part, g, prm, buf, lr, mu, DO_SGD);
+    net_gw_fold_range(i0, min(OFF_WF1 + 16050, i0 + 256), nch, part, g, prm, buf, lr, mu, DO_SGD);
     return;
   }
   // fc2 column slice; the last column also finalizes the loss partials
   // and advances the dropout seed (wave 0 only — no extra LDS).
   const int i0 = OFF_WF2 + (xcol - (T_CONV2 + T_CONV1 + T_FC1)) * 256;
-  net_gw_fold_range(i0, min(OFF_WF2 + 510, i0 + 256), nch, c1_ext, part,
+  net_gw_fold_range(i0, min(OFF_WF2 + 510, i0 + 256), nch, part,
                     g, prm, buf, lr, mu, DO_SGD);
   if (xcol == GW_TILES - 1 && threadIdx.x < 64) {
     if (loss_part) {
@@ -2219,7 +2196,7 @@ net_step_kernel(
   for (int t = wg; t < GW_TILES * nch; t += nblk) {
     const int tile = t % GW_TILES, ch = t / GW_TILES;
     const int b0 = ch * bchunk;
-    net_gw_tile(tile, tid, b0, min(B, b0 + bchunk), 8,
+    net_gw_tile(tile, tid, b0, min(B, b0 + bchunk),
                 part + (int64_t)ch * GW_ROW, x, p1_ws, p2_ws, d3_ws,
                 ga1_ws, ga2_ws, gh1_ws, glog_ws);
     __syncthreads();
@@ -2230,7 +2207,7 @@ net_step_kernel(
   const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
                       OFF_WF2, OFF_BF2, GW_TOTAL};
   for (int i = wg * 256 + tid; i < GW_TOTAL; i += nblk * 256) {
-    const float acc = net_gw_combine_elem(i, nch, nch, nch, 7, part);
+    const float acc = net_gw_combine_elem(i, nch, nch, nch, part);
     const int t = net_gw_tensor_of(i, off);
     const int64_t j = i - off[t];
     grd.p[t][j] = acc;
@@ -2502,12 +2479,9 @@ void sgd_step(const std::vector<uintptr_t>& ps,
 }
 
 
-// conv1 sub-block count: 8 three-row bands at small chunks (a cheap
-// combine fold), 24 single-row subs at large chunks (3x the blocks
-// where conv1 is the gw straggler) — r2 ledger.
-static inline int gw_c1_subs(int bchunk) { return bchunk <= 16 ? 8 : 24; }
-
-// gw chunk count: default 32 (or B when smaller); DTP_GW_NCH overrides.
+// gw chunk count (fc families; conv1 follows it, conv2 has its own):
+// 16 up to B=192, 24 above; DTP_GW_NCH overrides.  Re-swept with the
+// MFMA conv tiles (profiles/sweeps/mfma_gw_sweep.log).
 static int gw_nch(int B) {
   static int env_nch = -2;
   if (env_nch == -2) {
@@ -2518,11 +2492,13 @@ static int gw_nch(int B) {
   if (env_nch > 0) {
     nch = env_nch;
   } else if (B <= 192) {
-    nch = 16;   // B=128: 1.67M vs 1.61M at 32 (r2 sweep, post-rework)
-  } else if (B <= 768) {
-    nch = 24;   // B=512: 3.31M vs 3.06M at 32
+    nch = 16;   // B=128: 55.5 us vs 58.3 at 24, 61.7 at 32
   } else {
-    nch = 32;   // B>=1024: 32 still best (B=4096: 4.76M vs 4.61M at 24)
+    // B=512: 106.8 us at 24 vs 110.3 at 32.  The fc tiles want 24 rows
+    // at every larger batch too once conv2 keeps its own 32 (gw_nch2):
+    // B=1024 180.9 vs 189.9 us at the old uniform 32, B=2048 318.3 vs
+    // 337.5, B=4096 595 vs 634.
+    nch = 24;
   }
   if (nch > 32) nch = 32;  // the part workspace holds 32 rows (_ws)
   if (nch > B) nch = B;
@@ -2610,15 +2586,10 @@ static unsigned int* fwd_flags_buf(hipStream_t s) {
   return bufs[dev];
 }
 
-// conv2-family gw chunk count (DTP_GW_NCH2 overrides).  The conv2
-// pair-mode columns are the gw straggler at small B (20.2 us isolated
-// of the 29.5 us bundle at B=128, kernel_micro); running ONLY conv2 at
-// a higher chunk count buys its parallelism without the conv1
-// extension-fold cost that made a GLOBAL chunk increase lose.
-// conv1-family gw chunk count (DTP_GW_NCH1 overrides); 16.6 us
-// isolated at B=128 — the second straggler after conv2.  Its combine
-// cost scales with nch1 * c1_ext (extension rows), which is why the
-// global sweep rejected 32; family-local it can still pay.
+// conv1-family gw chunk count (DTP_GW_NCH1 overrides).  Its combine
+// cost scales with nch1 * 7 (extension rows): B=128 55.2 us at 16 vs
+// 58.1 at 24 and 61.9 at 32; B=1024 180.9 us at 24 vs 182.6 at 32 — so
+// it simply follows nch.
 static int gw_nch1(int B, int nch) {
   static int env_nch = -2;
   if (env_nch == -2) {
@@ -2631,16 +2602,19 @@ static int gw_nch1(int B, int nch) {
   return nch1;
 }
 
+// conv2-family gw chunk count (DTP_GW_NCH2 overrides): more rows = more
+// parallelism for the family with the most arithmetic, without paying
+// the fold cost on every other family.
 static int gw_nch2(int B, int nch) {
   static int env_nch = -2;
   if (env_nch == -2) {
     const char* e = std::getenv("DTP_GW_NCH2");
     env_nch = e ? std::atoi(e) : -1;
   }
-  // sweep (profiles/sweeps/nch2_sweep.log): B=128 nch2=24 74.6us vs 76.2 at
-  // the uniform 16 (+2.1%); 32 within noise of 24; B=512 nch2=32 LOSES
-  // (combine cost) — so only the small-batch band deviates from nch.
-  int nch2 = env_nch > 0 ? env_nch : (B <= 192 ? 24 : nch);
+  // sweep (profiles/sweeps/mfma_gw_sweep.log): B=128 nch2=24 55.2 us vs
+  // 56.1 at 32 and 56.9 at 16; from B=512 up the MFMA tile wants the
+  // most rows the workspace holds (B=512 105.8 us at 32 vs 106.8 at 24).
+  int nch2 = env_nch > 0 ? env_nch : (B <= 192 ? 24 : 32);
   if (nch2 > 32) nch2 = 32;  // part workspace holds 32 rows (_ws)
   if (nch2 > B) nch2 = B;
   return nch2;
@@ -2807,7 +2781,7 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
     GwPtrs none{};
     hipLaunchKernelGGL(net_gw_partial_fold_kernel<false>,
                        dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       gw_c1_subs(bchunk), (const float*)x,
+                       (const float*)x,
                        (const float*)p1_ws, (const float*)p2_ws,
                        (const float*)d3_ws, (const float*)ga1_ws,
                        (const float*)ga2_ws, (const float*)gh1_ws,
@@ -2818,7 +2792,7 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
     return;
   }
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream), gw_c1_subs(bchunk),
+                     dim3(256), 0, S(stream),
                      (const float*)x,
                      (const float*)p1_ws, (const float*)p2_ws,
                      (const float*)d3_ws, (const float*)ga1_ws,
@@ -2828,7 +2802,7 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
   hipLaunchKernelGGL(net_gw_combine_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, nch, nch1,
-                     nch2, gw_c1_subs(bchunk) - 1,
+                     nch2,
                      (const float*)loss_part, (float*)loss_out,
                      fwd_grid(B), sb);
 }
@@ -2890,7 +2864,7 @@ void net_fused_fwdbwd(
     auto* kern = sgd ? net_gw_partial_fold_kernel<true>
                      : net_gw_partial_fold_kernel<false>;
     hipLaunchKernelGGL(kern, dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       gw_c1_subs(bchunk), (const float*)x,
+                       (const float*)x,
                        (const float*)p1_ws, (const float*)p2_ws,
                        (const float*)d3_ws, (const float*)ga1_ws,
                        (const float*)ga2_ws, (const float*)gh1_ws,
@@ -2901,7 +2875,7 @@ void net_fused_fwdbwd(
     return;
   }
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream), gw_c1_subs(bchunk),
+                     dim3(256), 0, S(stream),
                      (const float*)x,
                      (const float*)p1_ws, (const float*)p2_ws,
                      (const float*)d3_ws, (const float*)ga1_ws,
@@ -2912,14 +2886,14 @@ void net_fused_fwdbwd(
     hipLaunchKernelGGL(net_gw_combine_kernel,
                        dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                        S(stream), (const float*)part_ws, gp, nch,
-                       nch1, nch2, gw_c1_subs(bchunk) - 1,
+                       nch1, nch2,
                        (const float*)loss_part, (float*)loss_out,
                        nblk, sb);
   } else {
     hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
                        dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                        S(stream), (const float*)part_ws, gp, pp, bp,
-                       nch, nch1, nch2, gw_c1_subs(bchunk) - 1,
+                       nch, nch1, nch2,
                        (float)lr, (float)mu, (const float*)loss_part,
                        (float*)loss_out, nblk, sb);
   }
@@ -2980,7 +2954,7 @@ void net_fused_bwd_sgd(uintptr_t x, uintptr_t w2, uintptr_t wf1,
   if (gw_fold_on()) {
     hipLaunchKernelGGL(net_gw_partial_fold_kernel<true>,
                        dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       gw_c1_subs(bchunk), (const float*)x,
+                       (const float*)x,
                        (const float*)p1_ws, (const float*)p2_ws,
                        (const float*)d3_ws, (const float*)ga1_ws,
                        (const float*)ga2_ws, (const float*)gh1_ws,
@@ -2991,7 +2965,7 @@ void net_fused_bwd_sgd(uintptr_t x, uintptr_t w2, uintptr_t wf1,
     return;
   }
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream), gw_c1_subs(bchunk),
+                     dim3(256), 0, S(stream),
                      (const float*)x,
                      (const float*)p1_ws, (const float*)p2_ws,
                      (const float*)d3_ws, (const float*)ga1_ws,
@@ -3001,7 +2975,7 @@ void net_fused_bwd_sgd(uintptr_t x, uintptr_t w2, uintptr_t wf1,
   hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, pp, bp,
-                     nch, nch1, nch2, gw_c1_subs(bchunk) - 1,
+                     nch, nch1, nch2,
                      (float)lr, (float)mu, (const float*)loss_part,
                      (float*)loss_out, fwd_grid(B), sb);
 }
@@ -3010,14 +2984,14 @@ void net_fused_bwd_sgd(uintptr_t x, uintptr_t w2, uintptr_t wf1,
 // in isolation)
 void net_gw_combine_raw(uintptr_t part_ws,
                         const std::vector<uintptr_t>& grd_v, int nch,
-                        int nch1, int nch2, int c1_ext,
+                        int nch1, int nch2,
                         uintptr_t stream) {
   GwPtrs gp{};
   for (int i = 0; i < 8; ++i) gp.p[i] = (float*)grd_v[i];
   hipLaunchKernelGGL(net_gw_combine_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, nch, nch1,
-                     nch2, c1_ext, nullptr, nullptr, 0, nullptr);
+                     nch2, nullptr, nullptr, 0, nullptr);
 }
 
 // raw combine+sgd launch (microbenchmarks)
@@ -3025,7 +2999,7 @@ void net_gw_combine_sgd_raw(uintptr_t part_ws,
                             const std::vector<uintptr_t>& grd_v,
                             const std::vector<uintptr_t>& prm_v,
                             const std::vector<uintptr_t>& buf_v,
-                            int nch, int nch1, int nch2, int c1_ext,
+                            int nch, int nch1, int nch2,
                             double lr,
                             double mu,
                             uintptr_t loss_part, uintptr_t loss_out,
@@ -3039,7 +3013,7 @@ void net_gw_combine_sgd_raw(uintptr_t part_ws,
   hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, pp, bp, nch,
-                     nch1, nch2, c1_ext, (float)lr, (float)mu,
+                     nch1, nch2, (float)lr, (float)mu,
                      (const float*)loss_part, (float*)loss_out,
                      nblk_fwd, nullptr);
 }
@@ -3055,7 +3029,7 @@ void net_gw_partial_raw(uintptr_t x, uintptr_t p1_ws, uintptr_t p2_ws,
                         int nch2, uintptr_t stream) {
   const int gy = std::max(nch, std::max(nch1, nch2));
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(ntiles, gy), dim3(256),
-                     0, S(stream), gw_c1_subs(bchunk), (const float*)x,
+                     0, S(stream), (const float*)x,
                      (const float*)p1_ws, (const float*)p2_ws,
                      (const float*)d3_ws, (const float*)ga1_ws,
                      (const float*)ga2_ws, (const float*)gh1_ws,

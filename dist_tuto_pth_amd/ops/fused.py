@@ -45,10 +45,10 @@ def _ws(B: int, device) -> Dict[str, torch.Tensor]:
             "p2": f(B, 320), "idx2": u8(B, 320), "h1": f(B, 50),
             "m3": u8(B, 50), "d3": f(B, 50), "logp": f(B, 10),
             "glog": f(B, 10), "gh1": f(B, 50), "ga2": f(B, 1280),
-            # partial rows are GW_ROW = 21840 + 23*260 wide (conv1's
-            # 24 weight-grad sub-blocks write disjoint slices;
+            # partial rows are GW_ROW = 21840 + 7*260 wide (conv1's
+            # 8 weight-grad sub-blocks write disjoint slices;
             # kernels.hip)
-            "ga1": f(B, 5760), "part": f(32, 27820), "loss": f(()),
+            "ga1": f(B, 5760), "part": f(32, 23660), "loss": f(()),
             # loss_part must cover the LARGEST forward grid any caller
             # can launch (grid_for(B,1) <= 4096) — sized once here so
             # every entry point shares a safe buffer regardless of
