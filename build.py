@@ -48,7 +48,8 @@ def build(force: bool = False):
         # (output, sources, extra flags)
         ("_rcclx.so", [os.path.join(CSRC, "rcclx.cpp")],
          ["-L/opt/rocm/lib", "-lrccl"]),
-        ("_kernels.so", [os.path.join(CSRC, "kernels.hip")], []),
+        ("_kernels.so", [os.path.join(CSRC, "kernels.hip"),
+                         os.path.join(CSRC, "linear_bf16.hip")], []),
     ]
     for out_name, srcs, extra in targets:
         out = os.path.join(OUT, out_name)

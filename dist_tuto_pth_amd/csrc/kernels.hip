@@ -3244,6 +3244,9 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 
 }  // namespace
 
+// K16 (bf16 MFMA linear, bf16 dropout) lives in linear_bf16.hip
+void register_linear_bf16(pybind11::module_& m);
+
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
   m.def("conv2d_fwd", &conv2d_fwd);
@@ -3280,4 +3283,5 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("copy_throttled", &copy_throttled);
   m.def("reduce_columns", &reduce_columns);
   m.def("scale_f32", &scale_f32);
+  register_linear_bf16(m);
 }

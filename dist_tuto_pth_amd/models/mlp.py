@@ -10,7 +10,7 @@ the training loop and the DP path.
 
 from __future__ import annotations
 
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -20,12 +20,24 @@ from .. import ops
 
 class MLP(nn.Module):
     """`widths` = [in, hidden..., out]; ReLU (fused into the linear
-    kernel) + dropout between layers, log_softmax output."""
+    kernel) + dropout between layers, log_softmax output.
+
+    ``compute_dtype=torch.bfloat16`` selects mixed precision: parameters
+    and their gradients stay fp32, every layer runs `ops.linear_bf16`
+    (bf16 operands on the matrix cores, fp32 accumulation), hidden
+    activations and dropout are bf16, and the last layer returns fp32
+    logits so the loss kernels are the fp32 ones."""
 
     def __init__(self, widths: Sequence[int] = (784, 256, 128, 10),
-                 dropout: float = 0.2):
+                 dropout: float = 0.2,
+                 compute_dtype: Optional[torch.dtype] = None):
         super().__init__()
         assert len(widths) >= 2
+        if compute_dtype not in (None, torch.bfloat16):
+            raise ValueError(
+                f"MLP: compute_dtype must be None or torch.bfloat16, "
+                f"got {compute_dtype}")
+        self.compute_dtype = compute_dtype
         self.widths = list(widths)
         self.p = dropout
         self.layers = nn.ModuleList(
@@ -35,7 +47,12 @@ class MLP(nn.Module):
         x = x.reshape(x.shape[0], self.widths[0])
         for i, lin in enumerate(self.layers):
             last = i == len(self.layers) - 1
-            x = ops.linear(x, lin.weight, lin.bias, fuse_relu=not last)
+            if self.compute_dtype is not None:
+                x = ops.linear_bf16(
+                    x, lin.weight, lin.bias, fuse_relu=not last,
+                    out_dtype=torch.float32 if last else torch.bfloat16)
+            else:
+                x = ops.linear(x, lin.weight, lin.bias, fuse_relu=not last)
             if not last:
                 x = ops.dropout(x, p=self.p, training=self.training)
         return x

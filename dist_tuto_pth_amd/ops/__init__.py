@@ -8,6 +8,7 @@ HIP kernel here (``csrc/kernels.hip``), with forward *and* backward:
   K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu
   K5/K6  dropout2d (channel) / dropout     -> dropout2d / dropout
   K7/K8  linear (+fused ReLU epilogue)     -> linear
+  K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
   K11-13 fused multi-tensor SGD+momentum   -> optim.FusedSGD
@@ -199,9 +200,10 @@ class _Dropout(torch.autograd.Function):
             else:
                 mask = torch.empty(x.numel(), device=x.device,
                                    dtype=torch.uint8)
-                k.dropout_fwd(x.data_ptr(), out.data_ptr(),
-                              mask.data_ptr(), x.numel(), p,
-                              _seed_ptr(x.device), _stream())
+                fwd = k.dropout_bf16_fwd if x.dtype == torch.bfloat16 \
+                    else k.dropout_fwd
+                fwd(x.data_ptr(), out.data_ptr(), mask.data_ptr(),
+                    x.numel(), p, _seed_ptr(x.device), _stream())
             ctx.save_for_backward(mask)
             ctx.meta = (scale, channelwise, x.shape)
             ctx.mask = mask
@@ -235,8 +237,10 @@ class _Dropout(torch.autograd.Function):
                 k.dropout2d_bwd(gy.data_ptr(), mask.data_ptr(),
                                 gx.data_ptr(), B * C, hw, scale, _stream())
             else:
-                k.dropout_bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(),
-                              gy.numel(), scale, _stream())
+                bwd = k.dropout_bf16_bwd if gy.dtype == torch.bfloat16 \
+                    else k.dropout_bwd
+                bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(),
+                    gy.numel(), scale, _stream())
             return gx, None, None, None
         if channelwise:
             B, C = shape[0], shape[1]
@@ -247,6 +251,13 @@ class _Dropout(torch.autograd.Function):
 
 
 def dropout(x, p=0.5, training=True):
+    """Elementwise dropout on fp32 or bf16 tensors.  The bf16 kernels hash
+    the same element index with the same device-side seed as the fp32
+    ones, so for equal seed and ``p`` the keep-mask is identical; kept
+    values are ``bf16(float(x) * scale)``."""
+    if x.is_cuda and x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(
+            f"ops.dropout: fp32 or bf16 CUDA tensors only, got {x.dtype}")
     return _Dropout.apply(x.contiguous(), p, training, False)
 
 
@@ -305,7 +316,141 @@ class _Linear(torch.autograd.Function):
 
 
 def linear(x, w, b=None, fuse_relu=False):
+    if x.is_cuda:
+        for name, t in (("x", x), ("w", w), ("b", b)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(
+                    f"ops.linear is fp32 only on GPU, got {name} of dtype "
+                    f"{t.dtype}; use ops.linear_bf16 for bf16 operands")
     return _Linear.apply(x.contiguous(), w, b, fuse_relu)
+
+
+# ---------------------------------------------------------------------------
+# K16 — mixed-precision linear: bf16 operands on the matrix cores, fp32
+# accumulation, fp32 master weights and gradients (csrc/linear_bf16.hip).
+# Contract, on GPU and CPU alike: every GEMM operand is bf16 (fp32 inputs
+# are rounded RNE first), products are summed in fp32, and each result is
+# rounded once to its output dtype.
+# ---------------------------------------------------------------------------
+def _to_bf16(t):
+    """RNE cast to a contiguous bf16 tensor (identity for bf16 input)."""
+    if t.dtype == torch.bfloat16:
+        return t.contiguous()
+    if t.dtype != torch.float32:
+        raise TypeError(f"linear_bf16: fp32 or bf16 tensors only, "
+                        f"got {t.dtype}")
+    if not t.is_cuda:
+        return t.contiguous().to(torch.bfloat16)
+    t = t.contiguous()
+    out = torch.empty(t.shape, device=t.device, dtype=torch.bfloat16)
+    _k().cast_f32_to_bf16(t.data_ptr(), out.data_ptr(), t.numel(),
+                          _stream())
+    return out
+
+
+class _LinearBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, fuse_relu, out_dtype):
+        # the bf16 copies are saved, so each operand is cast once per step
+        xb, wb = _to_bf16(x), _to_bf16(w)
+        B, K = xb.shape
+        N = wb.shape[0]
+        if x.is_cuda:
+            k = _k()
+            out = torch.empty(B, N, device=x.device, dtype=out_dtype)
+            k.linear_bf16_fwd(xb.data_ptr(), wb.data_ptr(),
+                              b.data_ptr() if b is not None else 0,
+                              out.data_ptr(), B, K, N, fuse_relu,
+                              out_dtype == torch.float32, _stream())
+        else:
+            acc = xb.float() @ wb.float().t()
+            if b is not None:
+                acc = acc + b
+            if fuse_relu:
+                acc = F.relu(acc)
+            out = acc.to(out_dtype)
+        ctx.save_for_backward(xb, wb, out if fuse_relu else None)
+        ctx.x_dtype, ctx.w_dtype = x.dtype, w.dtype
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        xb, wb, out = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        B, K = xb.shape
+        N = wb.shape[0]
+        gyb = _to_bf16(gy)
+        gx = gw = gb = None
+        if xb.is_cuda:
+            k = _k()
+            mask = out.data_ptr() if out is not None else 0
+            mask_f32 = out is not None and out.dtype == torch.float32
+            if need_x:
+                gx = torch.empty(B, K, device=xb.device, dtype=ctx.x_dtype)
+                k.linear_bf16_bwd_x(gyb.data_ptr(), wb.data_ptr(), mask,
+                                    mask_f32, gx.data_ptr(), B, K, N,
+                                    ctx.x_dtype == torch.float32, _stream())
+            if need_w or need_b:
+                gw = torch.empty(N, K, device=xb.device,
+                                 dtype=torch.float32)
+                gb = torch.empty(N, device=xb.device, dtype=torch.float32) \
+                    if need_b else None
+                splits = k.linear_bf16_gw_splits(B, K, N)
+                part = torch.empty(splits * (N * K + N), device=xb.device,
+                                   dtype=torch.float32) \
+                    if splits > 1 else None
+                k.linear_bf16_bwd_w(
+                    gyb.data_ptr(), xb.data_ptr(), mask, mask_f32,
+                    gw.data_ptr(), gb.data_ptr() if gb is not None else 0,
+                    part.data_ptr() if part is not None else 0, splits,
+                    B, K, N, _stream())
+                if ctx.w_dtype == torch.bfloat16:
+                    gw = _to_bf16(gw)
+                if not need_w:
+                    gw = None
+            return gx, gw, gb, None, None
+        g = gyb.float()
+        if out is not None:
+            g = g * (out > 0)
+        if need_x:
+            gx = (g @ wb.float()).to(ctx.x_dtype)
+        if need_w:
+            gw = (g.t() @ xb.float()).to(ctx.w_dtype)
+        if need_b:
+            gb = g.sum(0)
+        return gx, gw, gb, None, None
+
+
+def linear_bf16(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
+    """``relu?(x @ w.T + b)`` with bf16 operands and fp32 accumulation.
+
+    ``x`` [B,K] and ``w`` [N,K] are fp32 or bf16, ``b`` is fp32 or None;
+    the result is [B,N] in ``out_dtype`` (bf16 or fp32).  Backward gives
+    ``gx`` in ``x``'s dtype, ``gb`` in fp32, and ``gw`` in fp32 for an fp32
+    (master) weight — so optimizers and gradient all-reduce see exactly
+    the fp32 tensors they see on the fp32 path — or rounded once to bf16
+    for a bf16 weight.  The weight gradient is bitwise reproducible."""
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"linear_bf16: out_dtype must be torch.bfloat16 or "
+                        f"torch.float32, got {out_dtype}")
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"linear_bf16: x [B,K] and w [N,K] expected, got "
+                         f"{tuple(x.shape)} and {tuple(w.shape)}")
+    if min(x.shape[0], x.shape[1], w.shape[0]) < 1:
+        raise ValueError("linear_bf16: B, K and N must be >= 1")
+    for name, t in (("x", x), ("w", w)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"linear_bf16: {name} must be fp32 or bf16, "
+                            f"got {t.dtype}")
+    if b is not None:
+        if b.dtype != torch.float32:
+            raise TypeError(f"linear_bf16: b must be fp32, got {b.dtype}")
+        if b.shape != (w.shape[0],):
+            raise ValueError("linear_bf16: b must have shape [N]")
+        b = b.contiguous()
+    return _LinearBf16.apply(x, w, b, fuse_relu, out_dtype)
 
 
 # ---------------------------------------------------------------------------
