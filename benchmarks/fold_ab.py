@@ -7,7 +7,7 @@ per-rank compute of the world>1 DP step (net_fused_step: combine
 WITHOUT SGD, then the optimizer as its own dispatch after the — here
 absent — all-reduce), i.e. what every rank pays on the driver's
 multi-GPU scaling bench.  The fold variant folds the combine into the
-partial kernel's last-arriving blocks (kernels.hip), so it deletes one
+partial kernel's last-arriving blocks (net_fused.hip), so it deletes one
 dispatch from "ddp" and the combine+SGD dispatch from "sgd-fused".
 
 Run both shapes with DTP_GW_FOLD=0/1 before importing the package (the

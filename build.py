@@ -44,16 +44,16 @@ def build(force: bool = False):
     common = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17",
               "-fPIC", "-shared", "-fvisibility=hidden"] + inc
 
+    src = lambda *names: [os.path.join(CSRC, n) for n in names]  # noqa: E731
     targets = [
-        # (output, sources, extra flags)
-        ("_rcclx.so", [os.path.join(CSRC, "rcclx.cpp")],
-         ["-L/opt/rocm/lib", "-lrccl"]),
-        ("_kernels.so", [os.path.join(CSRC, "kernels.hip"),
-                         os.path.join(CSRC, "linear_bf16.hip")], []),
+        # (output, sources, headers, extra flags)
+        ("_rcclx.so", src("rcclx.cpp"), [], ["-L/opt/rocm/lib", "-lrccl"]),
+        ("_kernels.so", src("kernels.hip", "net_fused.hip",
+                            "linear_bf16.hip"), src("common.h"), []),
     ]
-    for out_name, srcs, extra in targets:
+    for out_name, srcs, hdrs, extra in targets:
         out = os.path.join(OUT, out_name)
-        if force or _needs_build(out, srcs):
+        if force or _needs_build(out, srcs + hdrs):
             _run(common + srcs + extra + ["-o", out])
         else:
             print(f"{out_name}: up to date")

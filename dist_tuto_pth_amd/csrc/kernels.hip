@@ -12,41 +12,19 @@
 // fp32 throughout (the reference trains fp32); bf16 enters for the
 // ring-allreduce reduction path (BASELINE config 5).
 // Build: hipcc --offload-arch=gfx950 (build.py).  No CUDA paths.
+//
+// This file also owns PYBIND11_MODULE; the fused whole-Net step
+// (net_fused.hip) and the bf16 linear (linear_bf16.hip) register their
+// bindings through register_net_fused() / register_linear_bf16().
 
-#include <hip/hip_runtime.h>
+#include "common.h"
+
 #include <hip/hip_bf16.h>
-#include <hip/hip_cooperative_groups.h>
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
-#include <cstdint>
-#include <cstdlib>
-#include <stdexcept>
-#include <string>
 #include <vector>
-
-namespace py = pybind11;
-
-#define HIP_CHECK(cmd)                                                        \
-  do {                                                                        \
-    hipError_t e_ = (cmd);                                                    \
-    if (e_ != hipSuccess)                                                     \
-      throw std::runtime_error(std::string("HIP error: ") +                   \
-                               hipGetErrorString(e_) + " @ " #cmd);           \
-  } while (0)
-
-static inline hipStream_t S(uintptr_t s) {
-  return reinterpret_cast<hipStream_t>(s);
-}
-
-static inline int grid_for(int64_t work, int block, int per_thread = 1) {
-  int64_t g = (work + (int64_t)block * per_thread - 1) /
-              ((int64_t)block * per_thread);
-  if (g > 4096) g = 4096;  // grid-stride beyond (G11: ~8 blocks/CU cap)
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // ===========================================================================
 // K1/K2 — direct convolution, stride 1, no padding (the only form Net
@@ -287,34 +265,16 @@ __global__ void relu_bwd_kernel(const float* __restrict__ gy,
 
 // ===========================================================================
 // K5/K6 — dropout.  Counter-based hash RNG (wang/xxhash-style mix of
-// (seed, index)): stateless, reproducible from the host-passed seed,
-// no RNG-state tensor.  Channelwise variant draws one number per
-// (batch, channel) plane (Dropout2d, train_dist.py:60).
+// (seed, index), mix32 in common.h): stateless, reproducible from the
+// device seed, no RNG-state tensor.  Channelwise variant draws one
+// number per (batch, channel) plane (Dropout2d, train_dist.py:60).
 // ===========================================================================
 // device-side seed bump: lets dropout RNG advance across hipGraph
 // replays (the seed lives in device memory; one tiny kernel increments
 // it before each dropout draw, stream-ordered).
 __global__ void bump_seed_kernel(unsigned long long* s) {
   if (threadIdx.x == 0 && blockIdx.x == 0)
-    *s += 0x9E3779B97F4A7C15ull;
-}
-
-// fused step prologue: advance the dropout seed (when training) and
-// zero the loss accumulator in ONE tiny launch instead of a bump
-// kernel + a hipMemsetAsync fill kernel (each ~4.5 us of pure launch
-// cost at the reference's batch sizes).
-__global__ void step_prologue_kernel(unsigned long long* s, float* loss) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    if (s) *s += 0x9E3779B97F4A7C15ull;
-    *loss = 0.f;
-  }
-}
-
-__device__ inline uint32_t mix32(uint64_t seed, uint64_t idx) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return (uint32_t)((z ^ (z >> 31)) >> 16);
+    *s += SEED_INC;
 }
 
 __global__ void dropout_fwd_kernel(const float* __restrict__ x,
@@ -802,1446 +762,11 @@ __global__ void copy_throttled_f32_kernel(float* __restrict__ dst,
     dst[i] = src[i];
 }
 
-// ===========================================================================
-// Fused whole-Net forward / backward (the launch-bound-regime lever).
-//
-// At the reference's batch sizes the per-op pipeline is bound by ~30
-// kernel launches of ~5 us each, not by arithmetic (rocprof profile,
-// profiles/).  These two kernels run the ENTIRE Net forward
-// (train_dist.py:64-71: conv1 -> pool+relu -> conv2 -> dropout2d ->
-// pool+relu -> fc1+relu -> dropout -> fc2 -> log_softmax -> NLL) and
-// the entire data backward in ONE kernel each, one workgroup per batch
-// element, activations staged through LDS; only the small per-batch
-// weight-gradient reductions stay as separate (chunked) kernels.
-// Architecture constants are Net's (SURVEY.md §2.1 'Net'): they are
-// hard-coded, which is the point — this is the flagship model's fast
-// path; the modular kernels above remain the general path.
-// ===========================================================================
-#define N_C1K 10        // conv1 out channels
-#define N_C2K 20        // conv2 out channels
-#define N_A1 (10*24*24) // conv1 out 5760
-#define N_P1 (10*12*12) // pool1 out 1440
-#define N_A2 (20*8*8)   // conv2 out 1280
-#define N_P2 320        // pool2 out (= fc1 in)
-#define N_H1 50         // fc1 out
-#define N_CLS 10        // classes
-
-// partial-row access, parameterized on coherence: the in-launch fold
-// variant stores partials sc1 (device-coherent, straight to the
-// coherence point) and reads them back sc1 — ZERO fences, so the
-// concurrently-running tile blocks keep their L1/L2 activation
-// locality.  The first fold attempt used the plain-store + agent
-// release/acquire recipe and measured 23-28% SLOWER end to end: one
-// `buffer_wbl2` L2 writeback per block x 1744 blocks evicted the very
-// activations the partial blocks re-read (ledger).  Partial traffic is
-// ~1.8 MB/step, so the slower sc1 store path is immaterial.
-template <bool SC1>
-__device__ __forceinline__ void gw_st(float* p, float v) {
-  if (SC1)
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    *p = v;
-}
-template <bool SC1>
-__device__ __forceinline__ float gw_ld(const float* p) {
-  if (SC1)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-  return *p;
-}
-
-// One sample's full forward (conv1..log_softmax+NLL) by one 256-thread
-// workgroup, activations staged through caller-provided LDS buffers.
-// Returns -— on tid 0 only — the sample's log-prob at the target
-// (callers accumulate the NLL loss); other lanes return 0.
-// Shared by net_fused_fwd_kernel and the single-launch net_step_kernel.
-// SPLIT mode (fused fwd at small B): TWO sibling workgroups per sample
-// fill the otherwise half-idle chip (B=128 launches 128 blocks on 256
-// CUs).  Both stage x/w1 and compute conv1+pool1 fully (duplicating
-// the cheap stage costs less than a second exchange), each computes
-// HALF of conv2's 20 output channels (and stages only its half of w2),
-// sibling 1 publishes its p2 half with sc1 stores + a per-sample flag
-// and exits; sibling 0 consumes it and runs fc1/fc2/softmax alone.
-// If the sibling is not yet resident (co-residency is not contractual)
-// sibling 0 falls back to computing the other half itself from its own
-// LDS p1 — identical values, so the duplicate global stores are benign
-// and the wait can never deadlock.
-template <bool SPLIT = false>
-__device__ __forceinline__ float net_fwd_sample(
-    int b, int tid, int B, int training, uint64_t seed,
-    int half, unsigned int* __restrict__ flag, unsigned int token,
-    const float* __restrict__ x,
-    const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2,
-    const float* __restrict__ wf1, const float* __restrict__ bf1,
-    const float* __restrict__ wf2, const float* __restrict__ bf2,
-    const int64_t* __restrict__ tgt,
-    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
-    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
-    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
-    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
-    float* __restrict__ logp_ws,
-    // LDS carve (sizes: 784, 260, 1440, 5020, 320, 50, 10)
-    float* xs, float* w1s, float* p1, float* w2s,
-    float* p2, float* d3, float* logits) {
-  float ret = 0.f;
-  {
-    // stage input + conv weights
-    for (int i = tid; i < 784; i += 256) xs[i] = x[(int64_t)b * 784 + i];
-    for (int i = tid; i < N_C1K * 25; i += 256) w1s[i] = w1[i];
-    if (tid < N_C1K) w1s[N_C1K * 25 + tid] = b1[tid];
-    {
-      const int wlo = SPLIT ? half * (N_C2K / 2) * 250 : 0;
-      const int whi = SPLIT ? wlo + (N_C2K / 2) * 250 : N_C2K * 250;
-      for (int i = wlo + tid; i < whi; i += 256) w2s[i] = w2[i];
-      const int klo = SPLIT ? half * (N_C2K / 2) : 0;
-      const int khi = SPLIT ? klo + N_C2K / 2 : N_C2K;
-      if (klo + tid < khi) w2s[N_C2K * 250 + klo + tid] = b2[klo + tid];
-    }
-    __syncthreads();
-
-    // conv1 + pool1 + relu in ONE register-blocked stage: each thread
-    // owns a 2x2 pooling window, computes its four conv outputs in
-    // four independent accumulator chains (the kernel is LDS-latency
-    // bound at ~1 wave/SIMD — profiles/), then pools in registers.
-    // The 5760-float conv1 activation never touches LDS.
-    for (int i = tid; i < N_P1; i += 256) {
-      const int c = i / 144, ph = (i / 12) % 12, pw = i % 12;
-      const float* wk = w1s + c * 25;
-      const float* xp = xs + ph * 2 * 28 + pw * 2;
-      const float bias = w1s[N_C1K * 25 + c];
-      float q00 = bias, q01 = bias, q10 = bias, q11 = bias;
-      #pragma unroll
-      for (int r = 0; r < 5; ++r) {
-        #pragma unroll
-        for (int s = 0; s < 5; ++s) {
-          const float w = wk[r * 5 + s];
-          const float* xr = xp + r * 28 + s;
-          q00 += xr[0] * w;
-          q01 += xr[1] * w;
-          q10 += xr[28] * w;
-          q11 += xr[29] * w;
-        }
-      }
-      int am = 0; float m = q00;
-      if (q01 > m) { m = q01; am = 1; }
-      if (q10 > m) { m = q10; am = 2; }
-      if (q11 > m) { m = q11; am = 3; }
-      const float o = m > 0.f ? m : 0.f;
-      p1[i] = o;
-      if (!SPLIT || half == 0) {
-        p1_ws[(int64_t)b * N_P1 + i] = o;
-        idx1_ws[(int64_t)b * N_P1 + i] =
-            (uint8_t)(m > 0.f ? am : (am | 4));
-      }
-    }
-    __syncthreads();
-
-    // conv2 + dropout2d + pool2 + relu, same register-blocked shape:
-    // one thread per pooled cell, four conv outputs in four chains,
-    // channel dropout applied in registers before the max.
-    const int c2lo = SPLIT ? half * (N_P2 / 2) : 0;
-    const int c2hi = SPLIT ? c2lo + N_P2 / 2 : N_P2;
-    for (int i = c2lo + tid; i < c2hi; i += 256) {
-      const int k = i / 16, ph = (i / 4) % 4, pw = i % 4;
-      const float bias = w2s[N_C2K * 250 + k];
-      float q00 = bias, q01 = bias, q10 = bias, q11 = bias;
-      #pragma unroll
-      for (int c = 0; c < 10; ++c) {
-        const float* pp = p1 + c * 144 + ph * 2 * 12 + pw * 2;
-        const float* wc = w2s + (k * 10 + c) * 25;
-        #pragma unroll
-        for (int r = 0; r < 5; ++r) {
-          #pragma unroll
-          for (int s = 0; s < 5; ++s) {
-            const float w = wc[r * 5 + s];
-            const float* pr = pp + r * 12 + s;
-            q00 += pr[0] * w;
-            q01 += pr[1] * w;
-            q10 += pr[12] * w;
-            q11 += pr[13] * w;
-          }
-        }
-      }
-      if (training) {
-        const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + k);
-        const float dsc = (rr >= 0x80000000u) ? 2.f : 0.f;
-        q00 *= dsc; q01 *= dsc; q10 *= dsc; q11 *= dsc;
-      }
-      int am = 0; float m = q00;
-      if (q01 > m) { m = q01; am = 1; }
-      if (q10 > m) { m = q10; am = 2; }
-      if (q11 > m) { m = q11; am = 3; }
-      const float o = m > 0.f ? m : 0.f;
-      p2[i] = o;
-      gw_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
-      idx2_ws[(int64_t)b * N_P2 + i] = (uint8_t)(m > 0.f ? am : (am | 4));
-    }
-    if ((!SPLIT || half == 0) && training && tid < N_C2K) {
-      const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + tid);
-      m2_ws[(int64_t)b * N_C2K + tid] = rr >= 0x80000000u;
-    }
-    __syncthreads();
-    if (SPLIT && half == 1) {
-      // publish: p2 half is sc1-stored (at the coherence point once
-      // vmcnt retires) — drain, then write this STEP's token.  A
-      // token (not a 0/1 flag) makes stale publishes harmless: if a
-      // fallback fired last step, this late write still never matches
-      // a later step's expected token, so no reset is ever needed.
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0)
-        __hip_atomic_store(flag, token, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      return 0.f;  // fc/softmax belong to sibling 0
-    }
-    if (SPLIT && half == 0) {
-      // consume the sibling's half: bounded poll for THIS step's
-      // token, then sc1 loads into our LDS p2.  On timeout compute
-      // the half ourselves (fallback — co-residency is the norm but
-      // not contractual).
-      __shared__ unsigned s_got;
-      if (tid == 0) {
-        unsigned got = 0;
-        for (int it = 0; it < 60000; ++it) {
-          if (__hip_atomic_load(flag, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_AGENT) == token) {
-            got = 1u;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(4);
-        }
-        if (got)  // consume: under hipGraph replay the token repeats,
-                  // so the next replay must wait for a fresh publish
-          __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        s_got = got;
-      }
-      __syncthreads();
-      if (s_got) {
-        for (int i = N_P2 / 2 + tid; i < N_P2; i += 256)
-          p2[i] = gw_ld<true>(p2_ws + (int64_t)b * N_P2 + i);
-      } else {  // sibling never ran: do its channels from our own p1
-        for (int i = N_P2 / 2 + tid; i < N_P2; i += 256) {
-          const int k = i / 16, ph = (i / 4) % 4, pw = i % 4;
-          float q00 = b2[k], q01 = q00, q10 = q00, q11 = q00;
-          #pragma unroll
-          for (int c = 0; c < 10; ++c) {
-            const float* pp = p1 + c * 144 + ph * 2 * 12 + pw * 2;
-            const float* wc = w2 + (k * 10 + c) * 25;  // global: our
-            #pragma unroll                             // w2s half only
-            for (int r = 0; r < 5; ++r) {
-              #pragma unroll
-              for (int s = 0; s < 5; ++s) {
-                const float w = wc[r * 5 + s];
-                const float* pr = pp + r * 12 + s;
-                q00 += pr[0] * w;
-                q01 += pr[1] * w;
-                q10 += pr[12] * w;
-                q11 += pr[13] * w;
-              }
-            }
-          }
-          if (training) {
-            const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + k);
-            const float dsc = (rr >= 0x80000000u) ? 2.f : 0.f;
-            q00 *= dsc; q01 *= dsc; q10 *= dsc; q11 *= dsc;
-          }
-          float m = fmaxf(fmaxf(q00, q01), fmaxf(q10, q11));
-          p2[i] = m > 0.f ? m : 0.f;
-        }
-      }
-      __syncthreads();
-    }
-
-    // fc1 (320->50) + relu + dropout: 4 threads per output, shfl reduce
-    if (tid < N_H1 * 4) {
-      const int n = tid >> 2, q = tid & 3;
-      const float* wr = wf1 + n * N_P2 + q * 80;
-      const float* pr = p2 + q * 80;
-      float e0 = 0.f, e1 = 0.f;
-      #pragma unroll 4
-      for (int k = 0; k < 80; k += 2) {
-        e0 += pr[k] * wr[k];
-        e1 += pr[k + 1] * wr[k + 1];
-      }
-      float acc = e0 + e1;
-      acc += __shfl_down(acc, 1, 4);
-      acc += __shfl_down(acc, 2, 4);
-      if (q == 0) {
-        float h = acc + bf1[n];
-        h = h > 0.f ? h : 0.f;
-        h1_ws[(int64_t)b * N_H1 + n] = h;
-        float dd = h;
-        uint8_t keep = 1;
-        if (training) {
-          const uint32_t rr = mix32(seed ^ 0x5bd1e995u,
-                                    (uint64_t)b * N_H1 + n);
-          keep = rr >= 0x80000000u;
-          dd = keep ? h * 2.f : 0.f;
-        }
-        m3_ws[(int64_t)b * N_H1 + n] = keep;
-        d3_ws[(int64_t)b * N_H1 + n] = dd;
-        d3[n] = dd;
-      }
-    }
-    __syncthreads();
-
-    // fc2 (50->10)
-    if (tid < N_CLS) {
-      const float* wr = wf2 + tid * N_H1;
-      float acc = bf2[tid];
-      #pragma unroll 10
-      for (int k = 0; k < N_H1; ++k) acc += d3[k] * wr[k];
-      logits[tid] = acc;
-    }
-    __syncthreads();
-
-    // log_softmax + NLL (one lane)
-    if (tid == 0) {
-      float m = logits[0];
-      #pragma unroll
-      for (int i = 1; i < N_CLS; ++i) m = fmaxf(m, logits[i]);
-      float ssum = 0.f;
-      #pragma unroll
-      for (int i = 0; i < N_CLS; ++i) ssum += __expf(logits[i] - m);
-      const float lse = m + __logf(ssum);
-      float lp_t = 0.f;
-      const int64_t t = tgt[b];
-      #pragma unroll
-      for (int i = 0; i < N_CLS; ++i) {
-        const float lp = logits[i] - lse;
-        logp_ws[(int64_t)b * N_CLS + i] = lp;
-        if (i == (int)t) lp_t = lp;
-      }
-      ret = lp_t;
-    }
-    __syncthreads();
-  }
-  return ret;
-}
-
-__global__ void
-__launch_bounds__(256)
-net_fused_fwd_kernel(
-    const float* __restrict__ x,      // [B,1,28,28]
-    const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2,
-    const float* __restrict__ wf1, const float* __restrict__ bf1,
-    const float* __restrict__ wf2, const float* __restrict__ bf2,
-    const int64_t* __restrict__ tgt,
-    float* __restrict__ p1_ws,        // [B,1440]
-    uint8_t* __restrict__ idx1_ws,    // [B,1440]
-    uint8_t* __restrict__ m2_ws,      // [B,20]
-    float* __restrict__ p2_ws,        // [B,320]
-    uint8_t* __restrict__ idx2_ws,    // [B,320]
-    float* __restrict__ h1_ws,        // [B,50]
-    uint8_t* __restrict__ m3_ws,      // [B,50]
-    float* __restrict__ d3_ws,        // [B,50]
-    float* __restrict__ logp_ws,      // [B,10]
-    float* __restrict__ loss,         // scalar (pre-zeroed) — legacy mode
-    float* __restrict__ loss_part,    // [gridDim.x] or null: when set,
-                                      // per-block partials (no atomics,
-                                      // no pre-zeroing; the combine
-                                      // kernel finalizes the loss)
-    const unsigned long long* __restrict__ seed_p,
-    int B, int training) {
-  __shared__ __attribute__((aligned(16))) float xs[784];
-  __shared__ float w1s[N_C1K * 25 + N_C1K];
-  __shared__ float p1[N_P1];
-  __shared__ float w2s[N_C2K * 10 * 25 + N_C2K];
-  __shared__ float p2[N_P2];
-  __shared__ float d3[N_H1];
-  __shared__ float logits[N_CLS];
-  const int tid = threadIdx.x;
-  const uint64_t seed = seed_p[0];
-
-  float lsum = 0.f;
-  for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    const float lp_t = net_fwd_sample(
-        b, tid, B, training, seed, 0, nullptr, 0u, x, w1, b1, w2, b2,
-        wf1,
-        bf1, wf2, bf2, tgt, p1_ws, idx1_ws, m2_ws, p2_ws, idx2_ws,
-        h1_ws, m3_ws, d3_ws, logp_ws, xs, w1s, p1, w2s, p2, d3, logits);
-    if (tid == 0) lsum += -lp_t / B;
-  }
-  if (tid == 0) {
-    if (loss_part) loss_part[blockIdx.x] = lsum;
-    else atomicAdd(loss, lsum);
-  }
-}
-
-// Two sibling workgroups per sample (small-B fused fwd: B=128 alone
-// leaves half the 256 CUs idle).  blockIdx.x = 2*b + half; sibling 1
-// computes conv2 channels 10..19, publishes its p2 half (sc1 + flag)
-// and exits; sibling 0 runs the rest.  Grid is exactly 2*B.
-__global__ void
-__launch_bounds__(256)
-net_fused_fwd_split_kernel(
-    const float* __restrict__ x,
-    const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2,
-    const float* __restrict__ wf1, const float* __restrict__ bf1,
-    const float* __restrict__ wf2, const float* __restrict__ bf2,
-    const int64_t* __restrict__ tgt,
-    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
-    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
-    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
-    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
-    float* __restrict__ logp_ws, float* __restrict__ loss,
-    float* __restrict__ loss_part,
-    const unsigned long long* __restrict__ seed_p,
-    int B, int training, unsigned int* __restrict__ flags,
-    unsigned int token) {
-  __shared__ __attribute__((aligned(16))) float xs[784];
-  __shared__ float w1s[N_C1K * 25 + N_C1K];
-  __shared__ float p1[N_P1];
-  __shared__ float w2s[N_C2K * 10 * 25 + N_C2K];
-  __shared__ float p2[N_P2];
-  __shared__ float d3[N_H1];
-  __shared__ float logits[N_CLS];
-  const int tid = threadIdx.x;
-  const uint64_t seed = seed_p[0];
-  const int b = blockIdx.x >> 1, half = blockIdx.x & 1;
-  const float lp_t = net_fwd_sample<true>(
-      b, tid, B, training, seed, half, flags + b, token, x, w1, b1, w2,
-      b2, wf1, bf1, wf2, bf2, tgt, p1_ws, idx1_ws, m2_ws, p2_ws,
-      idx2_ws, h1_ws, m3_ws, d3_ws, logp_ws, xs, w1s, p1, w2s, p2, d3,
-      logits);
-  if (tid == 0) {
-    const float lsum = half == 0 ? -lp_t / B : 0.f;
-    if (loss_part) loss_part[blockIdx.x] = lsum;
-    else if (half == 0) atomicAdd(loss, lsum);
-  }
-}
-
-// One (sample, sibling-half)'s data backward: loss grad -> g_a1 (conv1
-// output grad).  `split` sibling workgroups cooperate on each sample:
-// the cheap early stages (g_logits .. gd2p staging, ~35k FMA) are
-// recomputed by every sibling, the hot conv2-bwd_x stage (720k FMA) is
-// partitioned by pooled position.  w2s must be pre-staged with conv2's
-// weights (5000 floats) by the caller.  Shared by net_fused_bwd_kernel
-// and the single-launch net_step_kernel.
-__device__ __forceinline__ void net_bwd_sample(
-    int b, int half, int split, int tid, int B, int training, float sc,
-    const float* __restrict__ wf1, const float* __restrict__ wf2,
-    const int64_t* __restrict__ tgt,
-    const uint8_t* __restrict__ idx1_ws,
-    const uint8_t* __restrict__ m2_ws,
-    const uint8_t* __restrict__ idx2_ws,
-    const float* __restrict__ h1_ws,
-    const uint8_t* __restrict__ m3_ws,
-    const float* __restrict__ logp_ws,
-    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
-    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,
-    // LDS carve (sizes: 5000, 10, 50, 50, 320, 6080)
-    const float* w2s, float* glg, float* gd3, float* gh1, float* gp2,
-    float* gd2p) {
-  {
-    // g_logits = (exp(logp) - onehot) * gl / B
-    __syncthreads();
-    if (tid < N_CLS) {
-      const float lp = logp_ws[(int64_t)b * N_CLS + tid];
-      const float g = (__expf(lp) -
-                       (tid == (int)tgt[b] ? 1.f : 0.f)) * sc;
-      glg[tid] = g;
-      if (half == 0)
-        glog_ws[(int64_t)b * N_CLS + tid] = g;
-    }
-    __syncthreads();
-
-    // g_d3 = wf2^T g_logits ; through dropout + relu -> g_h1pre
-    if (tid < N_H1) {
-      float acc = 0.f;
-      #pragma unroll
-      for (int n = 0; n < N_CLS; ++n)
-        acc += wf2[n * N_H1 + tid] * glg[n];
-      gd3[tid] = acc;
-      float g = acc;
-      if (training) {
-        g = m3_ws[(int64_t)b * N_H1 + tid] ? g * 2.f : 0.f;
-      }
-      if (h1_ws[(int64_t)b * N_H1 + tid] <= 0.f) g = 0.f;
-      gh1[tid] = g;
-      if (half == 0)
-        gh1_ws[(int64_t)b * N_H1 + tid] = g;
-    }
-    __syncthreads();
-
-    // g_p2 = wf1^T g_h1pre  (320 outputs x 50), four accumulator
-    // chains over the reduction dim (wf1 rows are coalesced global
-    // reads; the single 50-deep load+FMA chain was latency-bound)
-    for (int i = tid; i < N_P2; i += 256) {
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-      #pragma unroll
-      for (int n = 0; n < 48; n += 4) {
-        a0 += wf1[n * N_P2 + i] * gh1[n];
-        a1 += wf1[(n + 1) * N_P2 + i] * gh1[n + 1];
-        a2 += wf1[(n + 2) * N_P2 + i] * gh1[n + 2];
-        a3 += wf1[(n + 3) * N_P2 + i] * gh1[n + 3];
-      }
-      a0 += wf1[48 * N_P2 + i] * gh1[48];
-      a1 += wf1[49 * N_P2 + i] * gh1[49];
-      gp2[i] = (a0 + a1) + (a2 + a3);
-    }
-    __syncthreads();
-
-    // pool2 bwd + dropout2d bwd -> g_a2, scattered STRAIGHT into the
-    // padded gd2p tile with dropout applied (r2: the old path staged
-    // through a dense gd2 buffer — zero + scatter + full re-read, an
-    // extra 2.5k LDS ops per sample for nothing; gd2 is gone)
-    for (int i = tid; i < N_C2K * 304; i += 256) gd2p[i] = 0.f;
-    __syncthreads();
-    for (int i = tid; i < N_P2; i += 256) {
-      const int c = i / 16, oh = (i / 4) % 4, ow = i % 4;
-      const uint8_t v = idx2_ws[(int64_t)b * N_P2 + i];
-      if (!(v & 4)) {
-        const int am = v & 3;
-        const int fr = oh * 2 + (am >> 1), fc = ow * 2 + (am & 1);
-        float g = gp2[i];
-        if (training)
-          g = m2_ws[(int64_t)b * N_C2K + c] ? g * 2.f : 0.f;
-        gd2p[c * 304 + (fr + 4) * 19 + (fc + 4)] = g;
-      }
-    }
-    __syncthreads();
-    if (half == 0) {  // stash the dense conv2-out grad for the gw pass
-      for (int i = tid; i < N_A2; i += 256) {
-        const int k = i / 64, oh = (i / 8) % 8, ow = i % 8;
-        ga2_ws[(int64_t)b * N_A2 + i] =
-            gd2p[k * 304 + (oh + 4) * 19 + (ow + 4)];
-      }
-    }
-    __syncthreads();
-
-    // conv2 bwd_x through the padded tile + pool1 bwd, register-blocked
-    // 4-wide: each thread owns FOUR horizontally-adjacent pooled
-    // positions (one accumulator chain each); a (k, r) row contributes
-    // 8 consecutive gd2p values shared by all four outputs, cutting
-    // LDS reads ~2.5x vs one-output-per-thread (the kernel is
-    // LDS-latency-bound at this occupancy — profiles/).  Each pooled
-    // position owns its 2x2 ga1 window exclusively, so all four slots
-    // are written with no zeroing pass.  Partitioned across the
-    // `split` sibling workgroups (360 strips divisible by 1/2/4/8).
-    const int seg = (N_P1 / 4) / split;
-    const int t_end = (half + 1) * seg;
-    for (int t = half * seg + tid; t < t_end; t += 256) {
-      const int c = t / 36, rem = t % 36;
-      const int h = rem / 3, wc0 = (rem % 3) * 4;
-      float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-      for (int k = 0; k < N_C2K; ++k) {
-        const float* gk = gd2p + k * 304;
-        const float* wk = w2s + (k * 10 + c) * 25;
-        #pragma unroll
-        for (int r = 0; r < 5; ++r) {
-          const float* row = gk + (h - r + 4) * 19 + wc0;
-          const float w0 = wk[r * 5 + 0], w1 = wk[r * 5 + 1];
-          const float w2v = wk[r * 5 + 2], w3 = wk[r * 5 + 3];
-          const float w4 = wk[r * 5 + 4];
-          const float e0 = row[0], e1 = row[1], e2 = row[2];
-          const float e3 = row[3], e4 = row[4], e5 = row[5];
-          const float e6 = row[6], e7 = row[7];
-          q0 += e4 * w0 + e3 * w1 + e2 * w2v + e1 * w3 + e0 * w4;
-          q1 += e5 * w0 + e4 * w1 + e3 * w2v + e2 * w3 + e1 * w4;
-          q2 += e6 * w0 + e5 * w1 + e4 * w2v + e3 * w3 + e2 * w4;
-          q3 += e7 * w0 + e6 * w1 + e5 * w2v + e4 * w3 + e3 * w4;
-        }
-      }
-      const float qq[4] = {q0, q1, q2, q3};
-      const int64_t ib = (int64_t)b * N_P1 + c * 144 + h * 12 + wc0;
-      float* gp_base = ga1_ws + (int64_t)b * N_A1 + c * 576 +
-                       h * 2 * 24 + wc0 * 2;
-      #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint8_t v = idx1_ws[ib + j];
-        const int am = v & 3;
-        const float g = (v & 4) ? 0.f : qq[j];
-        float* gp = gp_base + j * 2;
-        gp[0] = am == 0 ? g : 0.f;
-        gp[1] = am == 1 ? g : 0.f;
-        gp[24] = am == 2 ? g : 0.f;
-        gp[25] = am == 3 ? g : 0.f;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Fused data-gradient backward: from loss grad to g_a1 (conv1 output
-// grad) in one kernel; weight gradients are reduced afterwards by the
-// chunked partial/combine kernels over the stashes.
-__global__ void
-__launch_bounds__(256)
-net_fused_bwd_kernel(
-    const float* __restrict__ w2, const float* __restrict__ wf1,
-    const float* __restrict__ wf2,
-    const int64_t* __restrict__ tgt,
-    const float* __restrict__ gl,      // dLoss (device scalar)
-    const uint8_t* __restrict__ idx1_ws,
-    const uint8_t* __restrict__ m2_ws,
-    const uint8_t* __restrict__ idx2_ws,
-    const float* __restrict__ h1_ws,
-    const uint8_t* __restrict__ m3_ws,
-    const float* __restrict__ logp_ws,
-    float* __restrict__ glog_ws,       // [B,10]  (fc2 out grad)
-    float* __restrict__ gh1_ws,        // [B,50]  (fc1 pre-relu grad)
-    float* __restrict__ ga2_ws,        // [B,1280] (conv2 out grad)
-    float* __restrict__ ga1_ws,        // [B,5760] (conv1 out grad)
-    int B, int training, int split) {
-  __shared__ __attribute__((aligned(16))) float w2s[N_C2K * 250];
-  __shared__ float glg[N_CLS];
-  __shared__ float gd3[N_H1];
-  __shared__ float gh1[N_H1];
-  __shared__ float gp2[N_P2];
-  // zero-padded conv2-out grad [k][16][19]: entry (k,oh+4,ow+4) holds
-  // the conv2-out grad at [k][oh][ow]; the pad makes the transposed-
-  // conv window reads branch-free so the 500-FMA loop unrolls with
-  // ILP.  Row stride 19 (not 16): PMC measured 59.8% LDSBankConflict
-  // at B=4096 from the power-of-2 stride (profiles/pmc_r2.md); over
-  // the loop's (h, wc0) lane pattern a brute-force scan shows stride
-  // 19 is conflict-FREE on 64 banks (17 still left 3-way clusters).
-  __shared__ float gd2p[N_C2K * 304];
-  const int tid = threadIdx.x;
-
-  for (int i = tid; i < N_C2K * 250; i += 256) w2s[i] = w2[i];
-  const float sc = gl[0] / B;
-
-  for (int bb = blockIdx.x; bb < B * split; bb += gridDim.x) {
-    net_bwd_sample(bb / split, bb % split, split, tid, B, training, sc,
-                   wf1, wf2, tgt, idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws,
-                   logp_ws, glog_ws, gh1_ws, ga2_ws, ga1_ws,
-                   w2s, glg, gd3, gh1, gp2, gd2p);
-  }
-}
-
-// Combined forward + data-backward in ONE kernel (round-2 experiment,
-// VERDICT r1 #9).  In the training loop the loss gradient is the
-// constant 1, so sample b's data backward depends ONLY on sample b's
-// forward — both run in the same workgroup with a __syncthreads where
-// the inter-kernel dependency used to be.  Saves one ~4.5 us dispatch
-// and the w2 re-staging (5000 floats/WG) the separate bwd kernel pays.
-// Cost: the backward loses its `split` sibling-workgroup parallelism
-// (grid = B, not B*split), so at small B the chip is underfilled.
-// The backward LDS carve aliases the forward's dead buffers: total
-// 5020 (w2s, shared by both phases — same [k*10+c]*25 weight layout)
-// + 7168 floats = 47.7 KB/WG -> 3 WGs/CU.
-__global__ void
-__launch_bounds__(256)
-net_fused_fwdbwd_kernel(
-    const float* __restrict__ x,
-    const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2,
-    const float* __restrict__ wf1, const float* __restrict__ bf1,
-    const float* __restrict__ wf2, const float* __restrict__ bf2,
-    const int64_t* __restrict__ tgt,
-    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
-    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
-    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
-    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
-    float* __restrict__ logp_ws,
-    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
-    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,
-    float* __restrict__ loss_part,
-    const unsigned long long* __restrict__ seed_p, int B, int training) {
-  __shared__ __attribute__((aligned(16))) float w2s[N_C2K * 250 + N_C2K];
-  __shared__ __attribute__((aligned(16))) float pool[7168];
-  const int tid = threadIdx.x;
-  const uint64_t seed = seed_p[0];
-  // forward carve
-  float* xs = pool;              // 784
-  float* w1s = pool + 784;       // 260
-  float* p1 = pool + 1048;       // 1440  (784+260=1044 -> pad to 1048)
-  float* p2 = pool + 2488;       // 320
-  float* d3 = pool + 2808;       // 50
-  float* logits = pool + 2860;   // 10
-  // backward carve (aliased onto the forward's dead buffers)
-  float* gd2p = pool;            // 6080 (= 20 k-planes x 16 x 19)
-  float* gp2 = pool + 6080;      // 320
-  float* glg = pool + 6400;      // 10
-  float* gd3 = pool + 6412;      // 50
-  float* gh1 = pool + 6464;      // 50 -> 6514 (buffer 7168)
-  const float sc = 1.f / B;      // dLoss == 1 by construction
-
-  float lsum = 0.f;
-  for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    const float lp_t = net_fwd_sample(
-        b, tid, B, training, seed, 0, nullptr, 0u, x, w1, b1, w2, b2,
-        wf1,
-        bf1, wf2, bf2, tgt, p1_ws, idx1_ws, m2_ws, p2_ws, idx2_ws,
-        h1_ws, m3_ws, d3_ws, logp_ws, xs, w1s, p1, w2s, p2, d3, logits);
-    if (tid == 0) lsum += -lp_t / B;
-    __syncthreads();  // fwd LDS dead + this block's global stashes visible
-    net_bwd_sample(b, 0, 1, tid, B, training, sc, wf1, wf2, tgt,
-                   idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws, logp_ws,
-                   glog_ws, gh1_ws, ga2_ws, ga1_ws,
-                   w2s, glg, gd3, gh1, gp2, gd2p);
-    __syncthreads();  // bwd LDS dead before the next sample reuses pool
-  }
-  if (tid == 0) loss_part[blockIdx.x] = lsum;
-}
-
-// Per-chunk partial weight gradients for all four layers in ONE launch
-// (replaces 4 kernels + 8 memsets): grid.x walks tile segments
-// [conv2 | fc1 | conv1 | fc2], grid.y is the batch chunk; partials land
-// in part[chunk][21840] laid out exactly like the flat grad buffer
-// (parameter order conv1.w,b conv2.w,b fc1.w,b fc2.w,b).
-#define GW_TOTAL 21840
-#define OFF_W1 0          // 250
-#define OFF_B1 250        // 10
-#define OFF_W2 260        // 5000
-#define OFF_B2 5260       // 20
-#define OFF_WF1 5280      // 16000
-#define OFF_BF1 21280     // 50
-#define OFF_WF2 21330     // 500
-#define OFF_BF2 21830     // 10
-#define T_CONV2 8         // conv2 tiles: 32-column slices of (c,r,s | bias)
-#define T_FC1 63          // ceil(16050/256)
-#define T_CONV1 8         // conv1 sub-blocks: bands of 3 output rows
-#define T_FC2 2           // ceil(510/256)
-#define GW_TILES (T_CONV2 + T_FC1 + T_CONV1 + T_FC2)
-// conv1's 8 sub-blocks write disjoint 260-float slices: sub 0 to the
-// canonical [OFF_W1,OFF_B1] region, subs 1-7 to an extension past
-// GW_TOTAL; the combine kernel folds the extension back in.
-#define GW_ROW (GW_TOTAL + (T_CONV1 - 1) * 260)
-
-typedef float gw_f32x16 __attribute__((ext_vector_type(16)));
-typedef float gw_f32x4 __attribute__((ext_vector_type(4)));
-
-// conv2 weight gradient as an implicit GEMM on exact-fp32 MFMA
-// (v_mfma_f32_32x32x2_f32; numerics are a k-ordered fmaf chain):
-//   M = 20 output channels (rows 20..31 fed zeros),
-//   N = 250 (c,r,s) columns + the bias as column 250 (B = ones),
-//       cut into 8 tiles of 32 — ONE BLOCK PER COLUMN TILE, all 20
-//       channels, so a chunk row stages p1 8 x (<= 3 of 10 planes)
-//       instead of 10-20 x the whole plane,
-//   K = (b, oh, ow), 64 per sample, split over the 4 waves: wave w owns
-//       positions 16w..16w+15.  K order inside a wave is free as long as
-//       A and B agree, so MFMA step j (0..7) of lane half h is position
-//       16w + 8h + j, i.e. (oh, ow) = (2w + h, j): the A operand is 8
-//       CONTIGUOUS ga2 floats per lane (two float4 loads straight from
-//       global, prefetched one sample ahead) and the B operand 8
-//       contiguous LDS floats at a per-lane column base.
-// Operand lane map (32x32x2): lane l gives A[row l&31][k l>>5] and
-// B[k l>>5][col l&31]; D[row (reg&3) + 8*(reg>>2) + 4*(l>>5)][col l&31].
-// One accumulator tile per wave is enough: the 32x32x2 dependent-chain
-// latency equals its issue interval (64 clk).  The four K-slices are
-// summed once per chunk through LDS in a fixed order (deterministic).
-// Every accumulator index is compile-time (a runtime index spilled to
-// scratch and tripled this kernel once — r2 ledger).
-static_assert(T_CONV2 * 32 >= 251, "conv2 gw column tiles cover 250 + bias");
-template <bool SC1 = false>
-__device__ __forceinline__ void net_gw_conv2_mfma(
-    int nt, int tid, int b0, int b1, float* __restrict__ my,
-    const float* __restrict__ p1_ws, const float* __restrict__ ga2_ws) {
-  __shared__ __attribute__((aligned(16))) float sp1[2][3 * 144];
-  __shared__ float red[4][N_C2K * 32];
-  const int lane = tid & 63, w = tid >> 6;
-  const int col = lane & 31, h = lane >> 5;
-  const int n = nt * 32 + col;
-  // 32 consecutive columns touch at most 3 input channels
-  const int c_lo = (nt * 32) / 25;
-  const int c_hi = min(N_C1K - 1, (nt * 32 + 31) / 25);
-  const int nst4 = (c_hi - c_lo + 1) * 36;  // float4s to stage (<= 108)
-  // per-lane im2col base: c*144 + (oh + r)*12 + (ow + s), oh = 2w + h
-  int base = (2 * w + h) * 12;
-  if (n < 250) base += (n / 25 - c_lo) * 144 + ((n % 25) / 5) * 12 + n % 5;
-  const float bfix = (n == 250) ? 1.f : 0.f;  // bias column / padding
-  const int aoff = col * 64 + 16 * w + 8 * h;
-  gw_f32x16 acc;
-  #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-  // b0 < b1 guard: ceil-rounded chunk counts leave EMPTY tail rows for
-  // non-divisible B (e.g. B=100, nch=16, bchunk=7 -> row 15 starts at
-  // sample 105); such a row must touch no memory and flush zeros.
-  if (b0 < b1) {
-    if (tid < nst4)
-      reinterpret_cast<float4*>(sp1[0])[tid] =
-          reinterpret_cast<const float4*>(
-              p1_ws + (int64_t)b0 * N_P1 + c_lo * 144)[tid];
-    if (col < N_C2K) {
-      const float4* ap = reinterpret_cast<const float4*>(
-          ga2_ws + (int64_t)b0 * N_A2 + aoff);
-      a0 = ap[0];
-      a1 = ap[1];
-    }
-  }
-  __syncthreads();
-  for (int b = b0; b < b1; ++b) {
-    const int cur = (b - b0) & 1;
-    // next sample: global loads issued before the MFMAs, LDS write after
-    const bool more = b + 1 < b1;
-    float4 st = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 n0 = st, n1 = st;
-    if (more) {
-      if (tid < nst4)
-        st = reinterpret_cast<const float4*>(
-            p1_ws + (int64_t)(b + 1) * N_P1 + c_lo * 144)[tid];
-      if (col < N_C2K) {
-        const float4* ap = reinterpret_cast<const float4*>(
-            ga2_ws + (int64_t)(b + 1) * N_A2 + aoff);
-        n0 = ap[0];
-        n1 = ap[1];
-      }
-    }
-    const float* bp = sp1[cur] + base;
-    float bv[8];
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) bv[j] = (n < 250) ? bp[j] : bfix;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, bv[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, bv[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, bv[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, bv[3], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, bv[4], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, bv[5], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, bv[6], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, bv[7], acc, 0, 0, 0);
-    if (more && tid < nst4)
-      reinterpret_cast<float4*>(sp1[cur ^ 1])[tid] = st;
-    a0 = n0;
-    a1 = n1;
-    __syncthreads();
-  }
-  // rows (channels) 0..19 of this wave's K-slice -> red[w][k][col]
-  #pragma unroll
-  for (int reg = 0; reg < 12; ++reg) {
-    const int k = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-    if (reg < 8 || h == 0) red[w][k * 32 + col] = acc[reg];
-  }
-  __syncthreads();
-  for (int i = tid; i < N_C2K * 32; i += 256) {
-    const int k = i >> 5, nn = nt * 32 + (i & 31);
-    const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    if (nn < 250)
-      gw_st<SC1>(my + OFF_W2 + k * 250 + nn, v);
-    else if (nn == 250)
-      gw_st<SC1>(my + OFF_B2 + k, v);
-  }
-}
-
-// conv1 weight gradient on exact-fp32 MFMA (v_mfma_f32_16x16x4_f32):
-//   M = 10 output channels (pad 16), N = 25 (r,s) + the bias as column
-//   25 (B = ones), pad 32 = two 16-wide tiles sharing the A operand,
-//   K = (b, oh, ow).  Sub-block `sub` of T_CONV1 owns a band of
-//   24/T_CONV1 output rows; inside it the (sample, row) pairs are dealt
-//   round-robin to the 4 waves.  One row = 24 positions = 6 MFMA steps:
-//   step j of lane group q = l>>4 is ow = 6q + j, so each lane reads 6
-//   contiguous ga1 floats (A) and 6 contiguous x floats per tile (B)
-//   straight from global — these re-reads are L1 hits (r2 ledger), and
-//   there is no barrier in the K loop.
-// Lane map (16x16x4): A[row l&15][k l>>4], B[k l>>4][col l&15];
-// D[row 4*(l>>4) + reg][col l&15].  Two independent accumulator tiles
-// per wave cover the 40-clk dependent latency (32-clk issue).
-template <bool SC1 = false>
-__device__ __forceinline__ void net_gw_conv1_mfma(
-    int sub, int tid, int b0, int b1, float* __restrict__ my,
-    const float* __restrict__ x, const float* __restrict__ ga1_ws) {
-  __shared__ float red[4][260];
-  const int lane = tid & 63, w = tid >> 6;
-  const int m = lane & 15, q = lane >> 4;
-  constexpr int rows = 24 / T_CONV1;
-  static_assert(rows * T_CONV1 == 24, "conv1 bands tile the 24 rows");
-  const int oh0 = sub * rows;
-  const int n1 = 16 + m;  // second tile: 16..24 weights, 25 bias, 26.. pad
-  const int xo0 = (m / 5) * 28 + m % 5 + 6 * q;
-  const int xo1 = (n1 < 25) ? (n1 / 5) * 28 + n1 % 5 + 6 * q : 0;
-  const float bfix = (n1 == 25) ? 1.f : 0.f;
-  const int ao = m * 576 + 6 * q;
-  gw_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int ntask = (b1 > b0) ? (b1 - b0) * rows : 0;
-  for (int t = w; t < ntask; t += 4) {
-    const int bb = t / rows;
-    const int b = b0 + bb, oh = oh0 + (t - bb * rows);
-    float av[6], v0[6], v1[6];
-    if (m < N_C1K) {
-      const float2* gp = reinterpret_cast<const float2*>(
-          ga1_ws + (int64_t)b * N_A1 + ao + oh * 24);
-      const float2 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-      av[0] = g0.x; av[1] = g0.y; av[2] = g1.x;
-      av[3] = g1.y; av[4] = g2.x; av[5] = g2.y;
-    } else {
-      #pragma unroll
-      for (int j = 0; j < 6; ++j) av[j] = 0.f;
-    }
-    const float* xp = x + (int64_t)b * 784 + oh * 28;
-    #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      v0[j] = xp[xo0 + j];
-      v1[j] = (n1 < 25) ? xp[xo1 + j] : bfix;
-    }
-    #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], v0[j], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], v1[j], acc1, 0, 0, 0);
-    }
-  }
-  #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int k = 4 * q + reg;
-    if (k < N_C1K) {
-      red[w][k * 25 + m] = acc0[reg];
-      if (n1 < 25) red[w][k * 25 + n1] = acc1[reg];
-      if (n1 == 25) red[w][250 + k] = acc1[reg];
-    }
-  }
-  __syncthreads();
-  // sub 0 writes the canonical region, subs 1.. the extension rows
-  float* dst = (sub == 0) ? (my + OFF_W1)
-                          : (my + GW_TOTAL + (sub - 1) * 260);
-  for (int i = tid; i < 260; i += 256)
-    gw_st<SC1>(dst + i,
-               (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
-}
-
-// One (tile, batch-chunk) partial weight-gradient reduction.  Tiles
-// walk [conv2 x8 | conv1 x8 | fc1 | fc2]; partials land in my[GW_ROW]
-// laid out like the flat grad buffer.  Shared by net_gw_partial_kernel
-// and the single-launch net_step_kernel.
-template <bool SC1 = false>
-__device__ __forceinline__ void net_gw_tile(
-    int tile, int tid, int b0, int b1,
-    float* __restrict__ my,
-    const float* __restrict__ x,
-    const float* __restrict__ p1_ws,
-    const float* __restrict__ p2_ws,
-    const float* __restrict__ d3_ws,
-    const float* __restrict__ ga1_ws,
-    const float* __restrict__ ga2_ws,
-    const float* __restrict__ gh1_ws,
-    const float* __restrict__ glog_ws) {
-  if (tile < T_CONV2) {  // conv2: gw [20][10][5][5] + gb [20]
-    // one code path for every chunk size: a block is one 32-column
-    // slice of the implicit GEMM over ALL 20 output channels
-    net_gw_conv2_mfma<SC1>(tile, tid, b0, b1, my, p1_ws, ga2_ws);
-    return;
-  }
-  tile -= T_CONV2;
-  if (tile < T_CONV1) {  // conv1: gw [10][1][5][5] + gb [10]
-    // K (the 24 output rows x batch chunk) is split over T_CONV1
-    // sub-blocks; sub 0 writes the canonical region, subs 1.. the
-    // extension rows, which the combine folds.
-    net_gw_conv1_mfma<SC1>(tile, tid, b0, b1, my, x, ga1_ws);
-    return;
-  }
-  tile -= T_CONV1;
-  if (tile < T_FC1) {  // fc1: gw [50][320] + gb [50]
-    const int i = tile * 256 + tid;
-    if (i < 16050) {
-      float acc = 0.f;
-      if (i < 16000) {
-        const int n = i / N_P2, k = i % N_P2;
-        float ae = 0.f, ao = 0.f;
-        int b = b0;
-        for (; b + 1 < b1; b += 2) {
-          ae += gh1_ws[(int64_t)b * N_H1 + n] *
-                p2_ws[(int64_t)b * N_P2 + k];
-          ao += gh1_ws[(int64_t)(b + 1) * N_H1 + n] *
-                p2_ws[(int64_t)(b + 1) * N_P2 + k];
-        }
-        if (b < b1)
-          ae += gh1_ws[(int64_t)b * N_H1 + n] *
-                p2_ws[(int64_t)b * N_P2 + k];
-        acc = ae + ao;
-        gw_st<SC1>(my + OFF_WF1 + i, acc);
-      } else {
-        const int n = i - 16000;
-        for (int b = b0; b < b1; ++b)
-          acc += gh1_ws[(int64_t)b * N_H1 + n];
-        gw_st<SC1>(my + OFF_BF1 + n, acc);
-      }
-    }
-    return;
-  }
-  tile -= T_FC1;
-  {  // fc2: gw [10][50] + gb [10]
-    const int i = tile * 256 + tid;
-    if (i < 510) {
-      float acc = 0.f;
-      if (i < 500) {
-        const int n = i / N_H1, k = i % N_H1;
-        for (int b = b0; b < b1; ++b)
-          acc += glog_ws[(int64_t)b * N_CLS + n] *
-                 d3_ws[(int64_t)b * N_H1 + k];
-        gw_st<SC1>(my + OFF_WF2 + i, acc);
-      } else {
-        const int n = i - 500;
-        for (int b = b0; b < b1; ++b)
-          acc += glog_ws[(int64_t)b * N_CLS + n];
-        gw_st<SC1>(my + OFF_BF2 + n, acc);
-      }
-    }
-  }
-}
-
-__global__ void __launch_bounds__(256)
-net_gw_partial_kernel(const float* __restrict__ x,
-                      const float* __restrict__ p1_ws,
-                      const float* __restrict__ p2_ws,
-                      const float* __restrict__ d3_ws,
-                      const float* __restrict__ ga1_ws,
-                      const float* __restrict__ ga2_ws,
-                      const float* __restrict__ gh1_ws,
-                      const float* __restrict__ glog_ws,
-                      float* __restrict__ part,  // [max chunk][GW_ROW]
-                      int B, int bchunk, int bchunk1, int bchunk2,
-                      int nch, int nch1, int nch2, int tile_base) {
-  // conv1/conv2 run at their own chunk counts (they are the straggler
-  // families at small B); gridDim.y = max of the three, families idle
-  // on the rows beyond their own count (idle blocks are
-  // launch-granularity free)
-  const int tile = blockIdx.x + tile_base;
-  const bool c2 = tile < T_CONV2;
-  const bool c1 = tile >= T_CONV2 && tile < T_CONV2 + T_CONV1;
-  if ((int)blockIdx.y >= (c2 ? nch2 : c1 ? nch1 : nch)) return;
-  const int bc = c2 ? bchunk2 : c1 ? bchunk1 : bchunk;
-  net_gw_tile(tile, threadIdx.x, (int)blockIdx.y * bc,
-              min(B, ((int)blockIdx.y + 1) * bc),
-              part + (int64_t)blockIdx.y * GW_ROW,
-              x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws, glog_ws);
-}
-
-// combine: grads[i] = sum over chunks of part[c][i], written through
-// the 8 per-parameter pointers (which may alias one flat buffer).
-struct GwPtrs { float* p[8]; };
-// sum flat-grad element i over the nch chunk rows (+ conv1 extension)
-template <bool SC1 = false>
-__device__ __forceinline__ float net_gw_combine_elem(
-    int i, int nch, int nch1, int nch2,
-    const float* __restrict__ part) {
-  // four independent accumulator chains: the single 32-deep
-  // load+add chain was latency-bound (VALUBusy ~0, profiles/).
-  // nch1/nch2: the conv1/conv2 families may run at their OWN chunk
-  // counts (they are the gw stragglers at small B; more chunks = more
-  // parallelism there without paying their fold cost on every other
-  // family, which is what made a GLOBAL chunk increase lose) —
-  // conv1-region elements (i < 260, extensions included) fold nch1
-  // rows, conv2-region elements nch2 rows, everything else nch.
-  const int n = i < 260 ? nch1
-              : (i >= OFF_W2 && i < OFF_WF1) ? nch2 : nch;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int c = 0;
-  for (; c + 3 < n; c += 4) {
-    a0 += gw_ld<SC1>(part + (int64_t)c * GW_ROW + i);
-    a1 += gw_ld<SC1>(part + (int64_t)(c + 1) * GW_ROW + i);
-    a2 += gw_ld<SC1>(part + (int64_t)(c + 2) * GW_ROW + i);
-    a3 += gw_ld<SC1>(part + (int64_t)(c + 3) * GW_ROW + i);
-  }
-  for (; c < n; ++c) a0 += gw_ld<SC1>(part + (int64_t)c * GW_ROW + i);
-  if (i < 260) {  // conv1 sub-block extension rows (see GW_ROW)
-    // fully unrolled over the 7 rows — a runtime-bound loop here cost
-    // the combine 50% (8.1 -> 12.2 us, r2 ledger)
-    static_assert(T_CONV1 == 8, "extension fold is unrolled for 7 rows");
-    for (int c2 = 0; c2 < nch1; ++c2) {
-      const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-      a0 += gw_ld<SC1>(ext + i) + gw_ld<SC1>(ext + 4 * 260 + i);
-      a1 += gw_ld<SC1>(ext + 260 + i) + gw_ld<SC1>(ext + 5 * 260 + i);
-      a2 += gw_ld<SC1>(ext + 2 * 260 + i) + gw_ld<SC1>(ext + 6 * 260 + i);
-      a3 += gw_ld<SC1>(ext + 3 * 260 + i);
-    }
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-
-// quad-lane variant: four consecutive lanes cooperate on one flat-grad
-// element (lane q strides the chunk rows), combined with two xor
-// shuffles.  Quadruples the wave count of the combine kernels — at 86
-// one-element-per-thread blocks they left 2/3 of the SIMDs empty and
-// ran a latency-exposed 8-deep L2 chain (profiles/).  Returns the full
-// sum on EVERY lane of the quad (butterfly reduction).
-__device__ __forceinline__ float net_gw_combine_elem_quad(
-    int i, int q, int nch, int nch1, int nch2,
-    const float* __restrict__ part) {
-  const int n = i < 260 ? nch1
-              : (i >= OFF_W2 && i < OFF_WF1) ? nch2 : nch;
-  float a0 = 0.f, a1 = 0.f;
-  for (int c = q; c < n; c += 8)
-    a0 += part[(int64_t)c * GW_ROW + i];
-  for (int c = q + 4; c < n; c += 8)
-    a1 += part[(int64_t)c * GW_ROW + i];
-  if (i < 260) {  // conv1 extension rows, spread across the quad
-    // fully unrolled (see net_gw_combine_elem note)
-    if (q == 0) {
-      for (int c2 = 0; c2 < nch1; ++c2) {
-        const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-        a0 += ext[i] + ext[260 + i] + ext[2 * 260 + i] + ext[3 * 260 + i];
-        a1 += ext[4 * 260 + i] + ext[5 * 260 + i] + ext[6 * 260 + i];
-      }
-    }
-  }
-  float acc = a0 + a1;
-  acc += __shfl_xor(acc, 1, 4);
-  acc += __shfl_xor(acc, 2, 4);
-  return acc;
-}
-
-__device__ __forceinline__ int net_gw_tensor_of(int i, const int* off) {
-  int t = 0;
-  while (i >= off[t + 1]) ++t;
-  return t;
-}
-
-// finalize the per-block loss partials written by the forward kernel
-// (loss_part mode) and advance the dropout seed for the NEXT step —
-// runs in block 0 of a combine kernel, replacing the step-prologue
-// dispatch (~4.5 us device floor) entirely.  The seed convention is
-// bump-AFTER everywhere (both the loss_part and the legacy autograd
-// path): the step consumes the current seed, the combine advances it.
-__device__ __forceinline__ void net_loss_finalize(
-    const float* __restrict__ loss_part, float* __restrict__ loss_out,
-    int nblk_fwd, unsigned long long* seed_bump) {
-  if (loss_part) {
-    __shared__ float red[256];
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nblk_fwd; i += 256) v += loss_part[i];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    #pragma unroll
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-      if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss_out = red[0];
-  }
-  if (threadIdx.x == 0 && seed_bump)
-    *seed_bump += 0x9E3779B97F4A7C15ull;
-}
-
-__global__ void net_gw_combine_kernel(const float* __restrict__ part,
-                                      GwPtrs g, int nch, int nch1,
-                                      int nch2,
-                                      const float* __restrict__ loss_part,
-                                      float* __restrict__ loss_out,
-                                      int nblk_fwd,
-                                      unsigned long long* seed_bump) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int64_t t4 = blockIdx.x * blockDim.x + threadIdx.x;
-       t4 < (int64_t)GW_TOTAL * 4;
-       t4 += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
-    const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               part);
-    if (q == 0) {
-      const int t = net_gw_tensor_of(i, off);
-      g.p[t][i - off[t]] = acc;
-    }
-  }
-  if ((loss_part || seed_bump) && blockIdx.x == 0)
-    net_loss_finalize(loss_part, loss_out, nblk_fwd, seed_bump);
-}
-
-// combine + SGD in one dispatch (single-GPU training: there is no
-// gradient all-reduce between combine and the optimizer step, so the
-// ~4.5 us dispatch floor of the separate sgd_step_kernel is pure
-// overhead).  Writes the grad (so .grad stays inspectable), updates
-// the momentum buffer and the parameter exactly like sgd_step_kernel.
-__global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
-                                          GwPtrs g, GwPtrs prm,
-                                          GwPtrs buf, int nch, int nch1,
-                                          int nch2,
-                                          float lr,
-                                          float mu,
-                                          const float* __restrict__ loss_part,
-                                          float* __restrict__ loss_out,
-                                          int nblk_fwd,
-                                          unsigned long long* seed_bump) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int64_t t4 = blockIdx.x * blockDim.x + threadIdx.x;
-       t4 < (int64_t)GW_TOTAL * 4;
-       t4 += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
-    const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               part);
-    if (q == 0) {
-      const int t = net_gw_tensor_of(i, off);
-      const int64_t j = i - off[t];
-      g.p[t][j] = acc;
-      float v = acc;
-      if (buf.p[t]) {
-        v = mu * buf.p[t][j] + acc;
-        buf.p[t][j] = v;
-      }
-      prm.p[t][j] -= lr * v;
-    }
-  }
-  if ((loss_part || seed_bump) && blockIdx.x == 0)
-    net_loss_finalize(loss_part, loss_out, nblk_fwd, seed_bump);
-}
-
-// ---------------------------------------------------------------------------
-// In-launch gw fold (r2): the combine dispatch is pure latency (~10 us at
-// B=128 — 86 tiny blocks, an L2-chain fold of 1.4 MB of partials), so this
-// variant of the partial kernel deletes it: the LAST-ARRIVING block of each
-// tile column folds the region its column wrote (and, DO_SGD, applies the
-// momentum update), using the split-K last-arriver recipe from the CDNA
-// guide (G16): every block drains vmcnt + __syncthreads, lane 0 issues an
-// agent-scope RELEASE fence, restates the vmcnt wait, THEN takes a relaxed
-// agent-scope ticket; the block that draws target-1 acquires (agent) and
-// reads every row with plain loads.  Fold regions are per COLUMN (what the
-// column's own blocks wrote), so counter==target implies the region's rows
-// are all visible:
-//   conv2 column t  -> columns 32t..32t+31 of (c,r,s | bias), all 20
-//                      output channels
-//   conv1 family    -> ONE counter over all T_CONV1*nch blocks (its
-//                      sub-blocks share the 260 outputs via extension rows,
-//                      so no single column's completion suffices)
-//   fc1/fc2 column j -> its 256-element flat slice
-// Each fold runs as soon as ITS column's blocks are done — overlapped with
-// the other families still computing — so the only exposed cost is the
-// straggler family's own (tiny) fold.
-__device__ __forceinline__ void net_gw_fold_one(
-    int i, int nch, const float* __restrict__ part,
-    const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
-    float mu, bool do_sgd) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  const float acc = net_gw_combine_elem<true>(i, nch, nch, nch, part);
-  const int t = net_gw_tensor_of(i, off);
-  const int64_t j = i - off[t];
-  g.p[t][j] = acc;
-  if (do_sgd) {
-    float v = acc;
-    if (buf.p[t]) {
-      v = mu * buf.p[t][j] + acc;
-      buf.p[t][j] = v;
-    }
-    prm.p[t][j] -= lr * v;
-  }
-}
-
-__device__ __forceinline__ void net_gw_fold_range(
-    int i0, int i1, int nch, const float* __restrict__ part,
-    const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
-    float mu, bool do_sgd) {
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256)
-    net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, do_sgd);
-}
-
-template <bool DO_SGD>
-__global__ void __launch_bounds__(256)
-net_gw_partial_fold_kernel(const float* __restrict__ x,
-                           const float* __restrict__ p1_ws,
-                           const float* __restrict__ p2_ws,
-                           const float* __restrict__ d3_ws,
-                           const float* __restrict__ ga1_ws,
-                           const float* __restrict__ ga2_ws,
-                           const float* __restrict__ gh1_ws,
-                           const float* __restrict__ glog_ws,
-                           float* __restrict__ part, int B, int bchunk,
-                           GwPtrs g, GwPtrs prm, GwPtrs buf, float lr,
-                           float mu, const float* __restrict__ loss_part,
-                           float* __restrict__ loss_out, int nblk_fwd,
-                           unsigned long long* seed_bump,
-                           unsigned int* __restrict__ cnt) {
-  const int b0 = blockIdx.y * bchunk;
-  net_gw_tile<true>(blockIdx.x, threadIdx.x, b0, min(B, b0 + bchunk),
-                    part + (int64_t)blockIdx.y * GW_ROW,
-                    x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws,
-                    glog_ws);
-  // ---- last-arriver ticket, FENCE-FREE: the tile wrote its partials
-  // with sc1 stores (already at the coherence point once vmcnt
-  // retires), so the ticket needs only the vmcnt drain before it and
-  // the reducer reads the rows back with sc1 loads.  No buffer_wbl2 /
-  // buffer_inv anywhere — the concurrent tile blocks keep their
-  // L1/L2-resident activations (the fenced variant cost 23-28%).
-  const int nch = (int)gridDim.y;
-  const int xcol = (int)blockIdx.x;
-  const bool conv1_fam = (xcol >= T_CONV2 && xcol < T_CONV2 + T_CONV1);
-  const int ci = conv1_fam ? T_CONV2 : xcol;
-  const unsigned target =
-      conv1_fam ? (unsigned)(T_CONV1 * nch) : (unsigned)nch;
-  __shared__ unsigned s_tk;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_tk = __hip_atomic_fetch_add(&cnt[ci], 1u, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (s_tk != target - 1) return;  // not the last arriver of this region
-  if (threadIdx.x == 0)
-    __hip_atomic_store(&cnt[ci], 0u, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);  // re-arm for next step
-  __syncthreads();
-  if (xcol < T_CONV2) {  // conv2: this column's 32-wide slice, all k
-    for (int e = (int)threadIdx.x; e < N_C2K * 32; e += 256) {
-      const int k = e >> 5, nn = xcol * 32 + (e & 31);
-      if (nn > 250) continue;
-      const int i = nn < 250 ? OFF_W2 + k * 250 + nn : OFF_B2 + k;
-      net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, DO_SGD);
-    }
-    return;
-  }
-  if (conv1_fam) {  // conv1: canonical 260 + extension rows
-    net_gw_fold_range(0, 260, nch, part, g, prm, buf, lr, mu,
-                      DO_SGD);
-    return;
-  }
-  if (xcol < T_CONV2 + T_CONV1 + T_FC1) {  // fc1 column slice
-    const int i0 = OFF_WF1 + (xcol - (T_CONV2 + T_CONV1)) * 256;
-    net_gw_fold_range(i0, min(OFF_WF1 + 16050, i0 + 256), nch, part, g, prm, buf, lr, mu, DO_SGD);
-    return;
-  }
-  // fc2 column slice; the last column also finalizes the loss partials
-  // and advances the dropout seed (wave 0 only — no extra LDS).
-  const int i0 = OFF_WF2 + (xcol - (T_CONV2 + T_CONV1 + T_FC1)) * 256;
-  net_gw_fold_range(i0, min(OFF_WF2 + 510, i0 + 256), nch, part,
-                    g, prm, buf, lr, mu, DO_SGD);
-  if (xcol == GW_TILES - 1 && threadIdx.x < 64) {
-    if (loss_part) {
-      float v = 0.f;
-      for (int i = threadIdx.x; i < nblk_fwd; i += 64) v += loss_part[i];
-      #pragma unroll
-      for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-      if (threadIdx.x == 0 && loss_out) *loss_out = v;
-    }
-    if (threadIdx.x == 0 && seed_bump)
-      *seed_bump += 0x9E3779B97F4A7C15ull;
-  }
-}
-
-// ===========================================================================
-// Single-launch training step (cooperative kernel).
-//
-// The 6-dispatch step (prologue, fwd, bwd, gw-partial, combine, sgd)
-// pays a ~4.5 us device dispatch floor per kernel at the reference's
-// batch sizes (rocprof, profiles/).  This kernel runs the WHOLE step —
-// forward, data backward, weight-gradient reduction, combine and the
-// SGD+momentum update — in ONE hipLaunchCooperativeKernel dispatch,
-// with cooperative-groups grid barriers between phases.  The per-phase
-// work is the same shared __device__ code as the modular kernels
-// (net_fwd_sample / net_bwd_sample / net_gw_tile / net_gw_combine_elem)
-// so numerics are identical by construction.
-//
-// The loss is accumulated per-workgroup (loss_part, no atomics and no
-// pre-zeroing) and summed into loss_out by workgroup 0 in the last
-// phase, which also advances the device dropout seed for the NEXT step
-// (replacing the step-prologue kernel; hipGraph-replay safe).
-//
-// When do_sgd == 0 the kernel stops after writing grads (the DP path:
-// host runs the flat-gradient all-reduce, then sgd_step_kernel).
-// ===========================================================================
-namespace cg = cooperative_groups;
-
-__global__ void __launch_bounds__(256)
-net_step_kernel(
-    const float* __restrict__ x,
-    const int64_t* __restrict__ tgt,
-    const float* __restrict__ gl,
-    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
-    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
-    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
-    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
-    float* __restrict__ logp_ws, float* __restrict__ glog_ws,
-    float* __restrict__ gh1_ws, float* __restrict__ ga2_ws,
-    float* __restrict__ ga1_ws, float* __restrict__ part,
-    float* __restrict__ loss_part,    // [gridDim.x]
-    float* __restrict__ loss_out,     // scalar
-    unsigned long long* __restrict__ seed_p,
-    GwPtrs prm, GwPtrs grd, GwPtrs buf,
-    float lr, float mu, int do_sgd,
-    int B, int training, int split, int bchunk, int nch) {
-  // LDS union: bwd carve (11,872 floats) reused by the fwd carve
-  // (7,884) and the final-phase reduction scratch; phases are
-  // separated by grid barriers.
-  __shared__ __attribute__((aligned(16))) float smem[12192];
-  float* xs = smem;             // 784
-  float* w1s = xs + 784;        // 260
-  float* p1 = w1s + 260;        // 1440
-  float* w2s = p1 + 1440;       // 5020 (fwd: w2+b2)
-  float* p2 = w2s + 5020;       // 320
-  float* d3 = p2 + 320;         // 50
-  float* logits = d3 + 50;      // 10
-  float* b_w2s = smem;          // 5000 (bwd: w2 only)
-  float* b_glg = smem + 5008;   // 10
-  float* b_gd3 = smem + 5024;   // 50
-  float* b_gh1 = smem + 5088;   // 50
-  float* b_gp2 = smem + 5152;   // 320
-  float* b_gd2p = smem + 5472;  // 6080 (20 x 16 x 19) -> 11552
-  const int tid = threadIdx.x;
-  const int wg = blockIdx.x, nblk = gridDim.x;
-  cg::grid_group grid = cg::this_grid();
-
-  const float* w1 = prm.p[0]; const float* b1 = prm.p[1];
-  const float* w2 = prm.p[2]; const float* b2 = prm.p[3];
-  const float* wf1 = prm.p[4]; const float* bf1 = prm.p[5];
-  const float* wf2 = prm.p[6]; const float* bf2 = prm.p[7];
-  const uint64_t seed = seed_p[0];
-
-  // ---- phase 1: forward ------------------------------------------------
-  float lsum = 0.f;
-  for (int b = wg; b < B; b += nblk) {
-    const float lp_t = net_fwd_sample(
-        b, tid, B, training, seed, 0, nullptr, 0u, x, w1, b1, w2, b2,
-        wf1,
-        bf1, wf2, bf2, tgt, p1_ws, idx1_ws, m2_ws, p2_ws, idx2_ws,
-        h1_ws, m3_ws, d3_ws, logp_ws, xs, w1s, p1, w2s, p2, d3, logits);
-    if (tid == 0) lsum += -lp_t / B;
-  }
-  if (tid == 0) loss_part[wg] = lsum;
-  grid.sync();
-
-  // ---- phase 2: data backward -----------------------------------------
-  for (int i = tid; i < N_C2K * 250; i += 256) b_w2s[i] = w2[i];
-  const float sc = gl[0] / B;
-  for (int bb = wg; bb < B * split; bb += nblk) {
-    net_bwd_sample(bb / split, bb % split, split, tid, B, training, sc,
-                   wf1, wf2, tgt, idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws,
-                   logp_ws, glog_ws, gh1_ws, ga2_ws, ga1_ws,
-                   b_w2s, b_glg, b_gd3, b_gh1, b_gp2, b_gd2p);
-  }
-  grid.sync();
-
-  // ---- phase 3: partial weight gradients ------------------------------
-  for (int t = wg; t < GW_TILES * nch; t += nblk) {
-    const int tile = t % GW_TILES, ch = t / GW_TILES;
-    const int b0 = ch * bchunk;
-    net_gw_tile(tile, tid, b0, min(B, b0 + bchunk),
-                part + (int64_t)ch * GW_ROW, x, p1_ws, p2_ws, d3_ws,
-                ga1_ws, ga2_ws, gh1_ws, glog_ws);
-    __syncthreads();
-  }
-  grid.sync();
-
-  // ---- phase 4: combine (+ SGD), loss finalize, seed bump --------------
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int i = wg * 256 + tid; i < GW_TOTAL; i += nblk * 256) {
-    const float acc = net_gw_combine_elem(i, nch, nch, nch, part);
-    const int t = net_gw_tensor_of(i, off);
-    const int64_t j = i - off[t];
-    grd.p[t][j] = acc;
-    if (do_sgd) {
-      float v = acc;
-      if (buf.p[t]) {
-        v = mu * buf.p[t][j] + acc;
-        buf.p[t][j] = v;
-      }
-      prm.p[t][j] -= lr * v;
-    }
-  }
-  if (wg == 0) {
-    float v = (tid < nblk) ? loss_part[tid] : 0.f;
-    if (tid + 256 < nblk) v += loss_part[tid + 256];  // nblk <= 512
-    smem[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (tid < s) smem[tid] += smem[tid + s];
-      __syncthreads();
-    }
-    if (tid == 0) {
-      *loss_out = smem[0];
-      if (training) *seed_p = seed + 0x9E3779B97F4A7C15ull;
-    }
-  }
-}
 
 // ===========================================================================
 // host launchers + pybind
 // ===========================================================================
 namespace {
-
-constexpr int BLK = 256;
 
 void conv2d_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
                 int B, int C, int H, int W, int K, int R, int S_,
@@ -2324,8 +849,7 @@ void relu_bwd(uintptr_t gy, uintptr_t out, uintptr_t gx, int64_t n,
 void dropout_fwd(uintptr_t x, uintptr_t out, uintptr_t mask, int64_t n,
                  double p, uintptr_t seed_dev, uintptr_t stream) {
   const float scale = 1.f / (1.f - (float)p);
-  hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(64), 0, S(stream),
-                     (unsigned long long*)seed_dev);
+  launch_bump_seed(seed_dev, S(stream));
   hipLaunchKernelGGL(dropout_fwd_kernel, dim3(grid_for(n, BLK)), dim3(BLK),
                      0, S(stream), (const float*)x, (float*)out,
                      (uint8_t*)mask, n, (float)p, scale,
@@ -2343,8 +867,7 @@ void dropout2d_fwd(uintptr_t x, uintptr_t out, uintptr_t mask,
                    int64_t planes, int64_t hw, double p,
                    uintptr_t seed_dev, uintptr_t stream) {
   const float scale = 1.f / (1.f - (float)p);
-  hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(64), 0, S(stream),
-                     (unsigned long long*)seed_dev);
+  launch_bump_seed(seed_dev, S(stream));
   hipLaunchKernelGGL(dropout2d_fwd_kernel,
                      dim3(grid_for(planes * hw, BLK)), dim3(BLK), 0,
                      S(stream), (const float*)x, (float*)out,
@@ -2479,726 +1002,6 @@ void sgd_step(const std::vector<uintptr_t>& ps,
 }
 
 
-// gw chunk count (fc families; conv1 follows it, conv2 has its own):
-// 16 up to B=192, 24 above; DTP_GW_NCH overrides.  Re-swept with the
-// MFMA conv tiles (profiles/sweeps/mfma_gw_sweep.log).
-static int gw_nch(int B) {
-  static int env_nch = -2;
-  if (env_nch == -2) {
-    const char* e = std::getenv("DTP_GW_NCH");
-    env_nch = e ? std::atoi(e) : -1;
-  }
-  int nch;
-  if (env_nch > 0) {
-    nch = env_nch;
-  } else if (B <= 192) {
-    nch = 16;   // B=128: 55.5 us vs 58.3 at 24, 61.7 at 32
-  } else {
-    // B=512: 106.8 us at 24 vs 110.3 at 32.  The fc tiles want 24 rows
-    // at every larger batch too once conv2 keeps its own 32 (gw_nch2):
-    // B=1024 180.9 vs 189.9 us at the old uniform 32, B=2048 318.3 vs
-    // 337.5, B=4096 595 vs 634.
-    nch = 24;
-  }
-  if (nch > 32) nch = 32;  // the part workspace holds 32 rows (_ws)
-  if (nch > B) nch = B;
-  return nch;
-}
-
-// in-launch gw fold (last-arriver epilogue in the partial kernel, no
-// combine dispatch).  DTP_GW_FOLD=1 opts in; the default stays the
-// two-kernel path — MEASURED NEGATIVE on both step shapes (ledger):
-// the combine's dispatch latency is hidden by the stream pipeline
-// (kernels enqueue back-to-back), so only its ~5 us execution is
-// exposed, while the epilogue's per-block sc1-drain tail costs ~4-5 us
-// across the critical path at B=128 (-5%); parity at B>=512.
-static bool gw_fold_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DTP_GW_FOLD");
-    v = (e && std::atoi(e) != 0) ? 1 : 0;
-  }
-  return v == 1;
-}
-
-// per-device ticket counters for the fold epilogue (GW_TILES u32,
-// zeroed once; each reducer re-arms its own counter every step)
-static unsigned int* gw_cnt_buf(hipStream_t s) {
-  static unsigned int* bufs[64] = {};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
-  if (!bufs[dev]) {
-    HIP_CHECK(hipMalloc(&bufs[dev], GW_TILES * sizeof(unsigned int)));
-    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, GW_TILES * sizeof(unsigned int),
-                             s));
-  }
-  return bufs[dev];
-}
-
-// fwd sibling split: 2 workgroups per sample when one per sample
-// cannot fill the 256 CUs.  DTP_FWD_SPLIT=1 forces off, =2 forces on.
-static int fwd_split(int B) {
-  static int env_v = -2;
-  if (env_v == -2) {
-    const char* e = std::getenv("DTP_FWD_SPLIT");
-    env_v = e ? std::atoi(e) : -1;
-  }
-  if (B * 2 > 4096) return 1;  // loss_part/flags hold 4096 entries
-  if (env_v == 1) return 1;
-  if (env_v == 2) return 2;
-  // 3-rep A/B (profiles/sweeps/fsplit_reps.log): +1.5% at B=64, +0.6% at
-  // B=128, -2.5% at B=192 (the pair grid exceeds the CU count there
-  // and the exchange round trip is pure overhead) — so the split is
-  // a small-batch lever only.
-  return B <= 128 ? 2 : 1;
-}
-
-// fwd grid size (the combine kernels fold loss_part over exactly this
-// many per-block partials)
-static int fwd_grid(int B) {
-  const int sp = fwd_split(B);
-  return sp == 2 ? 2 * B : grid_for(B, 1);
-}
-
-// monotone per-process token for the split-fwd handshake: each launch
-// publishes THIS value, so a stale write from a previous step's late
-// sibling can never satisfy a later step's wait.  (Never returns 0,
-// the flags' initial state.)
-static unsigned int fwd_token() {
-  static unsigned int t = 0;
-  if (++t == 0) ++t;
-  return t;
-}
-
-// per-device per-sample handshake flags for the split fwd (zeroed
-// once; published tokens are step-unique, no re-arm needed)
-static unsigned int* fwd_flags_buf(hipStream_t s) {
-  static unsigned int* bufs[64] = {};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
-  if (!bufs[dev]) {
-    HIP_CHECK(hipMalloc(&bufs[dev], 4096 * sizeof(unsigned int)));
-    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, 4096 * sizeof(unsigned int),
-                             s));
-  }
-  return bufs[dev];
-}
-
-// conv1-family gw chunk count (DTP_GW_NCH1 overrides).  Its combine
-// cost scales with nch1 * 7 (extension rows): B=128 55.2 us at 16 vs
-// 58.1 at 24 and 61.9 at 32; B=1024 180.9 us at 24 vs 182.6 at 32 — so
-// it simply follows nch.
-static int gw_nch1(int B, int nch) {
-  static int env_nch = -2;
-  if (env_nch == -2) {
-    const char* e = std::getenv("DTP_GW_NCH1");
-    env_nch = e ? std::atoi(e) : -1;
-  }
-  int nch1 = env_nch > 0 ? env_nch : nch;
-  if (nch1 > 32) nch1 = 32;
-  if (nch1 > B) nch1 = B;
-  return nch1;
-}
-
-// conv2-family gw chunk count (DTP_GW_NCH2 overrides): more rows = more
-// parallelism for the family with the most arithmetic, without paying
-// the fold cost on every other family.
-static int gw_nch2(int B, int nch) {
-  static int env_nch = -2;
-  if (env_nch == -2) {
-    const char* e = std::getenv("DTP_GW_NCH2");
-    env_nch = e ? std::atoi(e) : -1;
-  }
-  // sweep (profiles/sweeps/mfma_gw_sweep.log): B=128 nch2=24 55.2 us vs
-  // 56.1 at 32 and 56.9 at 16; from B=512 up the MFMA tile wants the
-  // most rows the workspace holds (B=512 105.8 us at 32 vs 106.8 at 24).
-  int nch2 = env_nch > 0 ? env_nch : (B <= 192 ? 24 : 32);
-  if (nch2 > 32) nch2 = 32;  // part workspace holds 32 rows (_ws)
-  if (nch2 > B) nch2 = B;
-  return nch2;
-}
-
-void net_fused_fwd(uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t w2,
-                   uintptr_t b2, uintptr_t wf1, uintptr_t bf1,
-                   uintptr_t wf2, uintptr_t bf2, uintptr_t tgt,
-                   uintptr_t p1_ws, uintptr_t idx1_ws, uintptr_t m2_ws,
-                   uintptr_t p2_ws, uintptr_t idx2_ws, uintptr_t h1_ws,
-                   uintptr_t m3_ws, uintptr_t d3_ws, uintptr_t logp_ws,
-                   uintptr_t loss, uintptr_t loss_part,
-                   uintptr_t seed_dev, int B,
-                   bool training, uintptr_t stream) {
-  // legacy mode (loss_part == 0): prologue dispatch zeroes the loss
-  // scalar, fwd accumulates the loss atomically.  loss_part mode: no
-  // prologue — per-block partials, finalized by the combine kernel.
-  // Both modes bump the dropout seed AFTER the step, in the combine
-  // kernel of net_fused_bwd (one convention, so the autograd path and
-  // the fused-step path can interleave without mask reuse).
-  if (!loss_part)
-    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0,
-                       S(stream), (unsigned long long*)nullptr,
-                       (float*)loss);
-  if (fwd_split(B) == 2) {
-    hipLaunchKernelGGL(net_fused_fwd_split_kernel, dim3(2 * B), dim3(256),
-                       0, S(stream), (const float*)x, (const float*)w1,
-                       (const float*)b1, (const float*)w2,
-                       (const float*)b2, (const float*)wf1,
-                       (const float*)bf1, (const float*)wf2,
-                       (const float*)bf2, (const int64_t*)tgt,
-                       (float*)p1_ws, (uint8_t*)idx1_ws, (uint8_t*)m2_ws,
-                       (float*)p2_ws, (uint8_t*)idx2_ws, (float*)h1_ws,
-                       (uint8_t*)m3_ws, (float*)d3_ws, (float*)logp_ws,
-                       (float*)loss, (float*)loss_part,
-                       (const unsigned long long*)seed_dev, B,
-                       training ? 1 : 0, fwd_flags_buf(S(stream)),
-                       fwd_token());
-    return;
-  }
-  hipLaunchKernelGGL(net_fused_fwd_kernel, dim3(grid_for(B, 1)), dim3(256),
-                     0, S(stream), (const float*)x, (const float*)w1,
-                     (const float*)b1, (const float*)w2, (const float*)b2,
-                     (const float*)wf1, (const float*)bf1,
-                     (const float*)wf2, (const float*)bf2,
-                     (const int64_t*)tgt, (float*)p1_ws, (uint8_t*)idx1_ws,
-                     (uint8_t*)m2_ws, (float*)p2_ws, (uint8_t*)idx2_ws,
-                     (float*)h1_ws, (uint8_t*)m3_ws, (float*)d3_ws,
-                     (float*)logp_ws, (float*)loss, (float*)loss_part,
-                     (const unsigned long long*)seed_dev, B,
-                     training ? 1 : 0);
-}
-
-static void launch_linear_gw(uintptr_t xp, uintptr_t gyp, uintptr_t gw,
-                             uintptr_t gb, int B, int K, int N,
-                             uintptr_t stream) {
-  const int wn = N * K;
-  const int wtiles = (wn + BLK - 1) / BLK;
-  int bchunk = B;
-  while (bchunk > 1 && wtiles * ((B + bchunk - 1) / bchunk) < 512)
-    bchunk = (bchunk + 1) / 2;
-  const int nchunks = (B + bchunk - 1) / bchunk;
-  if (nchunks > 1) {
-    HIP_CHECK(hipMemsetAsync((void*)gw, 0, (size_t)wn * sizeof(float),
-                             S(stream)));
-    if (gb)
-      HIP_CHECK(hipMemsetAsync((void*)gb, 0, N * sizeof(float), S(stream)));
-  }
-  hipLaunchKernelGGL(linear_bwd_w_kernel, dim3(wtiles, nchunks), dim3(BLK),
-                     0, S(stream), (const float*)xp, (const float*)gyp,
-                     (const float*)nullptr, (float*)gw, (float*)gb, B, K,
-                     N, bchunk);
-}
-
-static void launch_conv_gw(uintptr_t xp, uintptr_t gyp, uintptr_t gw,
-                           uintptr_t gb, int B, int C, int H, int W, int K,
-                           uintptr_t stream) {
-  const int wn = K * C * 25;
-  const int wtiles = (wn + BLK - 1) / BLK;
-  int bchunk = B;
-  while (bchunk > 1 && wtiles * ((B + bchunk - 1) / bchunk) < 512)
-    bchunk = (bchunk + 1) / 2;
-  const int nchunks = (B + bchunk - 1) / bchunk;
-  if (nchunks > 1) {
-    HIP_CHECK(hipMemsetAsync((void*)gw, 0, (size_t)wn * sizeof(float),
-                             S(stream)));
-    if (gb)
-      HIP_CHECK(hipMemsetAsync((void*)gb, 0, K * sizeof(float), S(stream)));
-  }
-  hipLaunchKernelGGL(conv2d_bwd_w_kernel, dim3(wtiles, nchunks), dim3(BLK),
-                     0, S(stream), (const float*)xp, (const float*)gyp,
-                     (float*)gw, (float*)gb, B, C, H, W, K, 5, 5, bchunk);
-}
-
-void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
-                   uintptr_t tgt, uintptr_t gl,
-                   uintptr_t p1_ws, uintptr_t idx1_ws, uintptr_t m2_ws,
-                   uintptr_t p2_ws, uintptr_t idx2_ws, uintptr_t h1_ws,
-                   uintptr_t m3_ws, uintptr_t d3_ws, uintptr_t logp_ws,
-                   uintptr_t glog_ws, uintptr_t gh1_ws, uintptr_t ga2_ws,
-                   uintptr_t ga1_ws, uintptr_t part_ws,
-                   uintptr_t gw1, uintptr_t gb1, uintptr_t gw2,
-                   uintptr_t gb2, uintptr_t gwf1, uintptr_t gbf1,
-                   uintptr_t gwf2, uintptr_t gbf2, int B, bool training,
-                   uintptr_t loss_part, uintptr_t loss_out,
-                   uintptr_t seed_dev, uintptr_t stream) {
-  // enough sibling workgroups per sample to fill the 256 CUs
-  // (DTP_BWD_SPLIT=1/2/4/8 overrides, for microbenchmarks)
-  int split = 0;
-  if (const char* e = std::getenv("DTP_BWD_SPLIT")) split = std::atoi(e);
-  if (split != 1 && split != 2 && split != 4 && split != 8) {
-    // microbench (profiles/): with the 4-wide-blocked hot loop,
-    // split=2 at B=128 (256 workgroups, 180 strips each) is fastest
-    split = 1;
-    while (split < 8 && B * split < 256) split *= 2;
-  }
-  const int nblk = grid_for((int64_t)B * split, 1);
-  hipLaunchKernelGGL(net_fused_bwd_kernel, dim3(nblk), dim3(256),
-                     0, S(stream), (const float*)w2, (const float*)wf1,
-                     (const float*)wf2, (const int64_t*)tgt,
-                     (const float*)gl, (const uint8_t*)idx1_ws,
-                     (const uint8_t*)m2_ws, (const uint8_t*)idx2_ws,
-                     (const float*)h1_ws, (const uint8_t*)m3_ws,
-                     (const float*)logp_ws, (float*)glog_ws,
-                     (float*)gh1_ws, (float*)ga2_ws, (float*)ga1_ws, B,
-                     training ? 1 : 0, split);
-  bool adaptive = false;
-  if (const char* e = std::getenv("DTP_GW_ADAPTIVE"))
-    adaptive = std::atoi(e) != 0;
-  if (adaptive) {
-    // legacy path kept for comparison: per-op adaptive chunked
-    // reductions.  Measured 2.85 ms/step at B=4096 vs ~0.7 ms for the
-    // partial scheme (profiles/) — not the default at any batch size.
-    if (loss_part)
-      throw std::runtime_error("net_fused_bwd: loss_part mode needs "
-                               "the partial gw path");
-    launch_conv_gw(x, ga1_ws, gw1, gb1, B, 1, 28, 28, N_C1K, stream);
-    launch_conv_gw(p1_ws, ga2_ws, gw2, gb2, B, 10, 12, 12, N_C2K,
-                   stream);
-    launch_linear_gw(p2_ws, gh1_ws, gwf1, gbf1, B, N_P2, N_H1, stream);
-    launch_linear_gw(d3_ws, glog_ws, gwf2, gbf2, B, N_H1, N_CLS, stream);
-    return;
-  }
-  // one segmented partial kernel over <=32 batch chunks + one combine
-  // (no memsets, no atomics); any batch size.  DTP_GW_NCH overrides
-  // the chunk count (fewer chunks = less partial traffic for the
-  // combine, more batch per partial block — sweep on hardware).
-  const int nch = gw_nch(B);
-  const int bchunk = (B + nch - 1) / nch;
-  // fold path keeps uniform chunks (its per-column tickets assume it)
-  const int nch1 = gw_fold_on() ? nch : gw_nch1(B, nch);
-  const int nch2 = gw_fold_on() ? nch : gw_nch2(B, nch);
-  const int bchunk1 = (B + nch1 - 1) / nch1;
-  const int bchunk2 = (B + nch2 - 1) / nch2;
-  const int gw_gy = std::max(nch, std::max(nch1, nch2));
-  GwPtrs gp;
-  gp.p[0] = (float*)gw1; gp.p[1] = (float*)gb1;
-  gp.p[2] = (float*)gw2; gp.p[3] = (float*)gb2;
-  gp.p[4] = (float*)gwf1; gp.p[5] = (float*)gbf1;
-  gp.p[6] = (float*)gwf2; gp.p[7] = (float*)gbf2;
-  unsigned long long* sb = (training && seed_dev)
-      ? (unsigned long long*)seed_dev : nullptr;
-  if (gw_fold_on()) {
-    GwPtrs none{};
-    hipLaunchKernelGGL(net_gw_partial_fold_kernel<false>,
-                       dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       (const float*)x,
-                       (const float*)p1_ws, (const float*)p2_ws,
-                       (const float*)d3_ws, (const float*)ga1_ws,
-                       (const float*)ga2_ws, (const float*)gh1_ws,
-                       (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                       gp, none, none, 0.f, 0.f,
-                       (const float*)loss_part, (float*)loss_out,
-                       fwd_grid(B), sb, gw_cnt_buf(S(stream)));
-    return;
-  }
-  hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream),
-                     (const float*)x,
-                     (const float*)p1_ws, (const float*)p2_ws,
-                     (const float*)d3_ws, (const float*)ga1_ws,
-                     (const float*)ga2_ws, (const float*)gh1_ws,
-                     (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                     bchunk1, bchunk2, nch, nch1, nch2, 0);
-  hipLaunchKernelGGL(net_gw_combine_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                     S(stream), (const float*)part_ws, gp, nch, nch1,
-                     nch2,
-                     (const float*)loss_part, (float*)loss_out,
-                     fwd_grid(B), sb);
-}
-
-// Combined fwd+bwd (one dispatch) + gw partial + combine: a 3-dispatch
-// training step (vs 4 for fwd / bwd / partial / combine).  When prm_v
-// is non-empty the combine also applies the SGD+momentum update
-// (single-GPU: 3 dispatches total including the optimizer).
-void net_fused_fwdbwd(
-    uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t w2, uintptr_t b2,
-    uintptr_t wf1, uintptr_t bf1, uintptr_t wf2, uintptr_t bf2,
-    uintptr_t tgt,
-    uintptr_t p1_ws, uintptr_t idx1_ws, uintptr_t m2_ws, uintptr_t p2_ws,
-    uintptr_t idx2_ws, uintptr_t h1_ws, uintptr_t m3_ws, uintptr_t d3_ws,
-    uintptr_t logp_ws, uintptr_t glog_ws, uintptr_t gh1_ws,
-    uintptr_t ga2_ws, uintptr_t ga1_ws, uintptr_t part_ws,
-    const std::vector<uintptr_t>& grd_v,
-    const std::vector<uintptr_t>& prm_v,
-    const std::vector<uintptr_t>& buf_v,
-    double lr, double mu, int B, bool training,
-    uintptr_t loss_part, uintptr_t loss_out, uintptr_t seed_dev,
-    uintptr_t stream) {
-  if (grd_v.size() != 8)
-    throw std::runtime_error("net_fused_fwdbwd: expected 8 grad ptrs");
-  const int nblk = grid_for(B, 1);
-  hipLaunchKernelGGL(net_fused_fwdbwd_kernel, dim3(nblk), dim3(256), 0,
-                     S(stream), (const float*)x, (const float*)w1,
-                     (const float*)b1, (const float*)w2, (const float*)b2,
-                     (const float*)wf1, (const float*)bf1,
-                     (const float*)wf2, (const float*)bf2,
-                     (const int64_t*)tgt, (float*)p1_ws,
-                     (uint8_t*)idx1_ws, (uint8_t*)m2_ws, (float*)p2_ws,
-                     (uint8_t*)idx2_ws, (float*)h1_ws, (uint8_t*)m3_ws,
-                     (float*)d3_ws, (float*)logp_ws, (float*)glog_ws,
-                     (float*)gh1_ws, (float*)ga2_ws, (float*)ga1_ws,
-                     (float*)loss_part,
-                     (const unsigned long long*)seed_dev, B,
-                     training ? 1 : 0);
-  const int nch = gw_nch(B);
-  const int bchunk = (B + nch - 1) / nch;
-  // fold path keeps uniform chunks (its per-column tickets assume it)
-  const int nch1 = gw_fold_on() ? nch : gw_nch1(B, nch);
-  const int nch2 = gw_fold_on() ? nch : gw_nch2(B, nch);
-  const int bchunk1 = (B + nch1 - 1) / nch1;
-  const int bchunk2 = (B + nch2 - 1) / nch2;
-  const int gw_gy = std::max(nch, std::max(nch1, nch2));
-  GwPtrs gp{}, pp{}, bp{};
-  for (int i = 0; i < 8; ++i) gp.p[i] = (float*)grd_v[i];
-  const bool sgd = !prm_v.empty();
-  if (sgd) {
-    for (int i = 0; i < 8; ++i) {
-      pp.p[i] = (float*)prm_v[i];
-      bp.p[i] = (i < (int)buf_v.size()) ? (float*)buf_v[i] : nullptr;
-    }
-  }
-  unsigned long long* sb = (training && seed_dev)
-      ? (unsigned long long*)seed_dev : nullptr;
-  if (gw_fold_on()) {
-    auto* kern = sgd ? net_gw_partial_fold_kernel<true>
-                     : net_gw_partial_fold_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       (const float*)x,
-                       (const float*)p1_ws, (const float*)p2_ws,
-                       (const float*)d3_ws, (const float*)ga1_ws,
-                       (const float*)ga2_ws, (const float*)gh1_ws,
-                       (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                       gp, pp, bp, (float)lr, (float)mu,
-                       (const float*)loss_part, (float*)loss_out, nblk,
-                       sb, gw_cnt_buf(S(stream)));
-    return;
-  }
-  hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream),
-                     (const float*)x,
-                     (const float*)p1_ws, (const float*)p2_ws,
-                     (const float*)d3_ws, (const float*)ga1_ws,
-                     (const float*)ga2_ws, (const float*)gh1_ws,
-                     (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                     bchunk1, bchunk2, nch, nch1, nch2, 0);
-  if (!sgd) {
-    hipLaunchKernelGGL(net_gw_combine_kernel,
-                       dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                       S(stream), (const float*)part_ws, gp, nch,
-                       nch1, nch2,
-                       (const float*)loss_part, (float*)loss_out,
-                       nblk, sb);
-  } else {
-    hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
-                       dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                       S(stream), (const float*)part_ws, gp, pp, bp,
-                       nch, nch1, nch2,
-                       (float)lr, (float)mu, (const float*)loss_part,
-                       (float*)loss_out, nblk, sb);
-  }
-}
-
-// net_fused_bwd + the optimizer update fused into the combine kernel
-// (single-GPU path: no all-reduce between combine and step).  The
-// segmented-partial weight-gradient path handles any batch size.
-void net_fused_bwd_sgd(uintptr_t x, uintptr_t w2, uintptr_t wf1,
-                       uintptr_t wf2, uintptr_t tgt, uintptr_t gl,
-                       uintptr_t p1_ws, uintptr_t idx1_ws,
-                       uintptr_t m2_ws, uintptr_t p2_ws,
-                       uintptr_t idx2_ws, uintptr_t h1_ws,
-                       uintptr_t m3_ws, uintptr_t d3_ws,
-                       uintptr_t logp_ws, uintptr_t glog_ws,
-                       uintptr_t gh1_ws, uintptr_t ga2_ws,
-                       uintptr_t ga1_ws, uintptr_t part_ws,
-                       const std::vector<uintptr_t>& grd_v,
-                       const std::vector<uintptr_t>& prm_v,
-                       const std::vector<uintptr_t>& buf_v,
-                       double lr, double mu, int B, bool training,
-                       uintptr_t loss_part, uintptr_t loss_out,
-                       uintptr_t seed_dev, uintptr_t stream) {
-  if (grd_v.size() != 8 || prm_v.size() != 8)
-    throw std::runtime_error("net_fused_bwd_sgd: expected 8 pointers");
-  int split = 0;
-  if (const char* e = std::getenv("DTP_BWD_SPLIT")) split = std::atoi(e);
-  if (split != 1 && split != 2 && split != 4 && split != 8) {
-    split = 1;
-    while (split < 8 && B * split < 256) split *= 2;
-  }
-  const int nblk = grid_for((int64_t)B * split, 1);
-  hipLaunchKernelGGL(net_fused_bwd_kernel, dim3(nblk), dim3(256),
-                     0, S(stream), (const float*)w2, (const float*)wf1,
-                     (const float*)wf2, (const int64_t*)tgt,
-                     (const float*)gl, (const uint8_t*)idx1_ws,
-                     (const uint8_t*)m2_ws, (const uint8_t*)idx2_ws,
-                     (const float*)h1_ws, (const uint8_t*)m3_ws,
-                     (const float*)logp_ws, (float*)glog_ws,
-                     (float*)gh1_ws, (float*)ga2_ws, (float*)ga1_ws, B,
-                     training ? 1 : 0, split);
-  const int nch = gw_nch(B);
-  const int bchunk = (B + nch - 1) / nch;
-  // fold path keeps uniform chunks (its per-column tickets assume it)
-  const int nch1 = gw_fold_on() ? nch : gw_nch1(B, nch);
-  const int nch2 = gw_fold_on() ? nch : gw_nch2(B, nch);
-  const int bchunk1 = (B + nch1 - 1) / nch1;
-  const int bchunk2 = (B + nch2 - 1) / nch2;
-  const int gw_gy = std::max(nch, std::max(nch1, nch2));
-  GwPtrs gp{}, pp{}, bp{};
-  for (int i = 0; i < 8; ++i) {
-    gp.p[i] = (float*)grd_v[i];
-    pp.p[i] = (float*)prm_v[i];
-    bp.p[i] = (i < (int)buf_v.size()) ? (float*)buf_v[i] : nullptr;
-  }
-  unsigned long long* sb = (training && seed_dev)
-      ? (unsigned long long*)seed_dev : nullptr;
-  if (gw_fold_on()) {
-    hipLaunchKernelGGL(net_gw_partial_fold_kernel<true>,
-                       dim3(GW_TILES, nch), dim3(256), 0, S(stream),
-                       (const float*)x,
-                       (const float*)p1_ws, (const float*)p2_ws,
-                       (const float*)d3_ws, (const float*)ga1_ws,
-                       (const float*)ga2_ws, (const float*)gh1_ws,
-                       (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                       gp, pp, bp, (float)lr, (float)mu,
-                       (const float*)loss_part, (float*)loss_out,
-                       fwd_grid(B), sb, gw_cnt_buf(S(stream)));
-    return;
-  }
-  hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, gw_gy),
-                     dim3(256), 0, S(stream),
-                     (const float*)x,
-                     (const float*)p1_ws, (const float*)p2_ws,
-                     (const float*)d3_ws, (const float*)ga1_ws,
-                     (const float*)ga2_ws, (const float*)gh1_ws,
-                     (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                     bchunk1, bchunk2, nch, nch1, nch2, 0);
-  hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                     S(stream), (const float*)part_ws, gp, pp, bp,
-                     nch, nch1, nch2,
-                     (float)lr, (float)mu, (const float*)loss_part,
-                     (float*)loss_out, fwd_grid(B), sb);
-}
-
-// raw combine launch (microbenchmarks: time the combine/sgd dispatch
-// in isolation)
-void net_gw_combine_raw(uintptr_t part_ws,
-                        const std::vector<uintptr_t>& grd_v, int nch,
-                        int nch1, int nch2,
-                        uintptr_t stream) {
-  GwPtrs gp{};
-  for (int i = 0; i < 8; ++i) gp.p[i] = (float*)grd_v[i];
-  hipLaunchKernelGGL(net_gw_combine_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                     S(stream), (const float*)part_ws, gp, nch, nch1,
-                     nch2, nullptr, nullptr, 0, nullptr);
-}
-
-// raw combine+sgd launch (microbenchmarks)
-void net_gw_combine_sgd_raw(uintptr_t part_ws,
-                            const std::vector<uintptr_t>& grd_v,
-                            const std::vector<uintptr_t>& prm_v,
-                            const std::vector<uintptr_t>& buf_v,
-                            int nch, int nch1, int nch2,
-                            double lr,
-                            double mu,
-                            uintptr_t loss_part, uintptr_t loss_out,
-                            int nblk_fwd, uintptr_t stream) {
-  GwPtrs gp{}, pp{}, bp{};
-  for (int i = 0; i < 8; ++i) {
-    gp.p[i] = (float*)grd_v[i];
-    pp.p[i] = (float*)prm_v[i];
-    bp.p[i] = (i < (int)buf_v.size()) ? (float*)buf_v[i] : nullptr;
-  }
-  hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                     S(stream), (const float*)part_ws, gp, pp, bp, nch,
-                     nch1, nch2, (float)lr, (float)mu,
-                     (const float*)loss_part, (float*)loss_out,
-                     nblk_fwd, nullptr);
-}
-
-// raw tile-segment launch of the partial weight-gradient kernel
-// (microbenchmarks: time [conv2 | fc1 | conv1 | fc2] separately)
-void net_gw_partial_raw(uintptr_t x, uintptr_t p1_ws, uintptr_t p2_ws,
-                        uintptr_t d3_ws, uintptr_t ga1_ws,
-                        uintptr_t ga2_ws, uintptr_t gh1_ws,
-                        uintptr_t glog_ws, uintptr_t part_ws, int B,
-                        int bchunk, int bchunk1, int bchunk2,
-                        int tile_base, int ntiles, int nch, int nch1,
-                        int nch2, uintptr_t stream) {
-  const int gy = std::max(nch, std::max(nch1, nch2));
-  hipLaunchKernelGGL(net_gw_partial_kernel, dim3(ntiles, gy), dim3(256),
-                     0, S(stream), (const float*)x,
-                     (const float*)p1_ws, (const float*)p2_ws,
-                     (const float*)d3_ws, (const float*)ga1_ws,
-                     (const float*)ga2_ws, (const float*)gh1_ws,
-                     (const float*)glog_ws, (float*)part_ws, B, bchunk,
-                     bchunk1, bchunk2, nch, nch1, nch2, tile_base);
-}
-
-// cooperative grid-barrier cost probe: `nsync` grid.sync()s and
-// nothing else, at fwd-kernel-like occupancy (32 KB LDS, 256 thr).
-// Times the lever that decides whether mid-kernel sibling exchanges
-// (fwd split, SURVEY-future) can beat kernel boundaries.
-__global__ void __launch_bounds__(256)
-barrier_probe_kernel(int nsync, float* sink) {
-  __shared__ float smem[8192];
-  smem[threadIdx.x] = (float)threadIdx.x;
-  cg::grid_group grid = cg::this_grid();
-  for (int i = 0; i < nsync; ++i) grid.sync();
-  if (threadIdx.x == 0 && blockIdx.x == 0) sink[0] = smem[0];
-}
-
-void barrier_probe(int nblk, int nsync, uintptr_t sink, uintptr_t stream) {
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  int nsync_v = nsync;
-  float* sinkp = (float*)sink;
-  void* args[] = {&nsync_v, &sinkp};
-  HIP_CHECK(hipLaunchCooperativeKernel(
-      reinterpret_cast<const void*>(barrier_probe_kernel), dim3(nblk),
-      dim3(256), args, 0, S(stream)));
-}
-
-// hand-rolled resident-grid flag barrier probe (the guide's G16
-// last-arriver pattern: agent-scope acq/rel on a generation counter,
-// relaxed poll).  Launched cooperatively ONLY for the co-residency
-// guarantee; measures what a grid barrier costs without
-// cooperative-groups' sync machinery (17-42 us, see barrier_probe).
-__global__ void __launch_bounds__(256)
-flag_barrier_probe_kernel(int nsync, unsigned int* bar, float* sink) {
-  __shared__ float smem[8192];
-  smem[threadIdx.x] = (float)threadIdx.x;
-  for (int i = 0; i < nsync; ++i) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned int gen = __hip_atomic_load(
-          &bar[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned int arrived =
-          __hip_atomic_fetch_add(&bar[0], 1u, __ATOMIC_ACQ_REL,
-                                 __HIP_MEMORY_SCOPE_AGENT) + 1;
-      if (arrived == gridDim.x) {
-        __hip_atomic_store(&bar[0], 0u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&bar[1], 1u, __ATOMIC_RELEASE,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        while (__hip_atomic_load(&bar[1], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT) == gen)
-          __builtin_amdgcn_s_sleep(8);
-        (void)__hip_atomic_load(&bar[1], __ATOMIC_ACQUIRE,
-                                __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && blockIdx.x == 0) sink[0] = smem[0];
-}
-
-void flag_barrier_probe(int nblk, int nsync, uintptr_t bar,
-                        uintptr_t sink, uintptr_t stream) {
-  int nsync_v = nsync;
-  unsigned int* barp = (unsigned int*)bar;
-  float* sinkp = (float*)sink;
-  void* args[] = {&nsync_v, &barp, &sinkp};
-  HIP_CHECK(hipLaunchCooperativeKernel(
-      reinterpret_cast<const void*>(flag_barrier_probe_kernel),
-      dim3(nblk), dim3(256), args, 0, S(stream)));
-}
-
-// ---- single-launch training step (cooperative) --------------------------
-int net_step_max_blocks() {
-  static int cached = -2;
-  if (cached != -2) return cached;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { cached = 0; return 0; }
-  int coop = 0;
-  if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch,
-                            dev) != hipSuccess || !coop) {
-    cached = 0;
-    return 0;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, reinterpret_cast<const void*>(net_step_kernel), 256,
-          0) != hipSuccess || per_cu < 1) {
-    cached = 0;
-    return 0;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-    cached = 0;
-    return 0;
-  }
-  int nb = per_cu * prop.multiProcessorCount;
-  if (nb > 512) nb = 512;  // loss_part reduction handles <= 512
-  cached = nb;
-  return nb;
-}
-
-bool net_step_available() { return net_step_max_blocks() > 0; }
-
-void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
-              uintptr_t p1_ws, uintptr_t idx1_ws, uintptr_t m2_ws,
-              uintptr_t p2_ws, uintptr_t idx2_ws, uintptr_t h1_ws,
-              uintptr_t m3_ws, uintptr_t d3_ws, uintptr_t logp_ws,
-              uintptr_t glog_ws, uintptr_t gh1_ws, uintptr_t ga2_ws,
-              uintptr_t ga1_ws, uintptr_t part_ws, uintptr_t loss_part,
-              uintptr_t loss_out, uintptr_t seed_dev,
-              const std::vector<uintptr_t>& prm_v,
-              const std::vector<uintptr_t>& grd_v,
-              const std::vector<uintptr_t>& buf_v,
-              double lr, double mu, bool do_sgd, int B, bool training,
-              uintptr_t stream) {
-  const int nblk = net_step_max_blocks();
-  if (nblk < 1)
-    throw std::runtime_error(
-        "net_step: cooperative launch unavailable on this device");
-  if (prm_v.size() != 8 || grd_v.size() != 8)
-    throw std::runtime_error("net_step: expected 8 param/grad pointers");
-  int split = 1;
-  while (split < 8 && B * split < nblk) split *= 2;
-  int bchunk = (B + 31) / 32;
-  int nch = (B + bchunk - 1) / bchunk;
-  GwPtrs prm{}, grd{}, buf{};
-  for (int i = 0; i < 8; ++i) {
-    prm.p[i] = (float*)prm_v[i];
-    grd.p[i] = (float*)grd_v[i];
-    buf.p[i] = (i < (int)buf_v.size()) ? (float*)buf_v[i] : nullptr;
-  }
-  const float* xp = (const float*)x;
-  const int64_t* tgtp = (const int64_t*)tgt;
-  const float* glp = (const float*)gl;
-  float* p1p = (float*)p1_ws;
-  uint8_t* idx1p = (uint8_t*)idx1_ws;
-  uint8_t* m2p = (uint8_t*)m2_ws;
-  float* p2p = (float*)p2_ws;
-  uint8_t* idx2p = (uint8_t*)idx2_ws;
-  float* h1p = (float*)h1_ws;
-  uint8_t* m3p = (uint8_t*)m3_ws;
-  float* d3p = (float*)d3_ws;
-  float* logpp = (float*)logp_ws;
-  float* glogp = (float*)glog_ws;
-  float* gh1p = (float*)gh1_ws;
-  float* ga2p = (float*)ga2_ws;
-  float* ga1p = (float*)ga1_ws;
-  float* partp = (float*)part_ws;
-  float* lpartp = (float*)loss_part;
-  float* loutp = (float*)loss_out;
-  unsigned long long* seedp = (unsigned long long*)seed_dev;
-  float lrf = (float)lr, muf = (float)mu;
-  int do_sgd_i = do_sgd ? 1 : 0, Bi = B, tri = training ? 1 : 0;
-  void* args[] = {&xp, &tgtp, &glp, &p1p, &idx1p, &m2p, &p2p, &idx2p,
-                  &h1p, &m3p, &d3p, &logpp, &glogp, &gh1p, &ga2p, &ga1p,
-                  &partp, &lpartp, &loutp, &seedp, &prm, &grd, &buf,
-                  &lrf, &muf, &do_sgd_i, &Bi, &tri, &split, &bchunk,
-                  &nch};
-  HIP_CHECK(hipLaunchCooperativeKernel(
-      reinterpret_cast<const void*>(net_step_kernel), dim3(nblk),
-      dim3(256), args, 0, S(stream)));
-}
-
 void add_inplace(uintptr_t dst, uintptr_t src, int64_t n, int dtype,
                  uintptr_t stream) {
   if (dtype == 7) {  // ncclFloat32 numbering (dist wrapper's _DTYPE)
@@ -3244,7 +1047,14 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 
 }  // namespace
 
-// K16 (bf16 MFMA linear, bf16 dropout) lives in linear_bf16.hip
+void launch_bump_seed(uintptr_t seed_ptr, hipStream_t stream) {
+  hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(64), 0, stream,
+                     (unsigned long long*)seed_ptr);
+}
+
+// the fused whole-Net step lives in net_fused.hip, K16 (bf16 MFMA
+// linear, bf16 dropout) in linear_bf16.hip
+void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
@@ -3268,20 +1078,10 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("log_softmax_nll_fwd", &log_softmax_nll_fwd);
   m.def("log_softmax_nll_bwd", &log_softmax_nll_bwd);
   m.def("sgd_step", &sgd_step);
-  m.def("net_fused_fwd", &net_fused_fwd);
-  m.def("net_fused_bwd", &net_fused_bwd);
-  m.def("net_fused_fwdbwd", &net_fused_fwdbwd);
-  m.def("net_step", &net_step);
-  m.def("net_step_available", &net_step_available);
-  m.def("net_gw_partial_raw", &net_gw_partial_raw);
-  m.def("net_gw_combine_raw", &net_gw_combine_raw);
-  m.def("net_gw_combine_sgd_raw", &net_gw_combine_sgd_raw);
-  m.def("barrier_probe", &barrier_probe);
-  m.def("flag_barrier_probe", &flag_barrier_probe);
-  m.def("net_fused_bwd_sgd", &net_fused_bwd_sgd);
   m.def("add_inplace", &add_inplace);
   m.def("copy_throttled", &copy_throttled);
   m.def("reduce_columns", &reduce_columns);
   m.def("scale_f32", &scale_f32);
+  register_net_fused(m);
   register_linear_bf16(m);
 }

@@ -22,12 +22,9 @@
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_linear_bf16().
 
-#include <hip/hip_runtime.h>
+#include "common.h"
 
 #include <pybind11/pybind11.h>
-
-#include <cstdint>
-#include <stdexcept>
 
 namespace {
 
@@ -53,10 +50,6 @@ static_assert(BK == 64, "lds_col swizzles the 8 chunks of a 64-deep row");
 // Chunks stay whole, so fragment reads remain one aligned 16-byte read.
 __device__ __forceinline__ int lds_col(int row, int col) {
   return col ^ (((row >> 3) & 7) << 3);
-}
-
-static inline hipStream_t S(uintptr_t s) {
-  return reinterpret_cast<hipStream_t>(s);
 }
 
 __device__ __forceinline__ float bf2f(bf16_t v) {
@@ -310,20 +303,10 @@ __global__ void gw_combine_kernel(const float* __restrict__ part,
 }
 
 // ---------------------------------------------------------------------------
-// bf16 elementwise dropout: same RNG, same element index, same seed pointer
-// as the fp32 kernels in kernels.hip, so equal (seed, p) gives equal masks.
+// bf16 elementwise dropout: the RNG (mix32) and the seed advance
+// (launch_bump_seed) ARE the fp32 kernels' (common.h), and the element index
+// and seed pointer are the same, so equal (seed, p) gives equal masks.
 // ---------------------------------------------------------------------------
-__global__ void bump_seed_bf16_kernel(unsigned long long* s) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *s += 0x9E3779B97F4A7C15ull;
-}
-
-__device__ inline uint32_t mix32(uint64_t seed, uint64_t idx) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return (uint32_t)((z ^ (z >> 31)) >> 16);
-}
-
 __global__ void dropout_bf16_fwd_kernel(
     const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
     uint8_t* __restrict__ mask, int64_t n, float p, float scale,
@@ -469,8 +452,7 @@ void linear_bf16_bwd_w(uintptr_t gy, uintptr_t x, uintptr_t mask,
 void dropout_bf16_fwd(uintptr_t x, uintptr_t out, uintptr_t mask, int64_t n,
                       double p, uintptr_t seed_dev, uintptr_t stream) {
   const float scale = 1.f / (1.f - (float)p);
-  hipLaunchKernelGGL(bump_seed_bf16_kernel, dim3(1), dim3(64), 0, S(stream),
-                     (unsigned long long*)seed_dev);
+  launch_bump_seed(seed_dev, S(stream));
   hipLaunchKernelGGL(dropout_bf16_fwd_kernel, dim3(ew_grid(n)), dim3(NT), 0,
                      S(stream), (const bf16_t*)x, (bf16_t*)out,
                      (uint8_t*)mask, n, (float)p, scale,

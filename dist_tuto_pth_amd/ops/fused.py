@@ -5,10 +5,11 @@ one kernel for the entire forward (conv1..log_softmax+NLL,
 train_dist.py:64-71 + :120, conv+pool register-fused, per-block loss
 partials), one for the data backward (sibling-workgroup split,
 4-wide register-blocked transposed conv), one segmented partial
-weight-gradient kernel ([conv2|conv1x24|fc1|fc2] tiles x batch chunks),
-and one combine kernel that also finalizes the loss, advances the
-dropout seed, and (single-GPU) applies the SGD+momentum update.
-rocprof evidence and the optimization ladder live in profiles/.
+weight-gradient kernel ([conv2 x8 | conv1 x8 | fc1 | fc2] tiles x batch
+chunks), and one combine kernel that also finalizes the loss, advances
+the dropout seed, and (single-GPU) applies the SGD+momentum update.
+The kernels and their launchers are csrc/net_fused.hip; rocprof
+evidence and the optimization ladder live in profiles/.
 Numerically identical to the modular path in eval mode; dropout masks
 use the same device-seed stream but a different indexing, so
 train-mode losses match only in distribution.
@@ -23,40 +24,85 @@ seed.
 
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 
 from ..utils.native import load_native
 from . import _seed_ptr, _stream
 
-_ws_cache: Dict[Tuple, Dict[str, torch.Tensor]] = {}
 
+class _Workspace:
+    """Per-(batch size, device) buffers shared by every fused entry
+    point.  Read-only: the tensors are never replaced, so ``ptrs`` —
+    their addresses in the native module's ``ws_fields`` order, the one
+    vector every native call takes — stays valid for the process."""
 
-def _ws(B: int, device) -> Dict[str, torch.Tensor]:
-    key = (B, device.index)
-    w = _ws_cache.get(key)
-    if w is None:
+    __slots__ = ("_tensors", "ptrs")
+
+    def __init__(self, k, B: int, device):
         f = lambda *shape: torch.empty(*shape, device=device)  # noqa: E731
         u8 = lambda *shape: torch.empty(*shape, device=device,  # noqa: E731
                                         dtype=torch.uint8)
-        w = {
+        t = {
             "p1": f(B, 1440), "idx1": u8(B, 1440), "m2": u8(B, 20),
             "p2": f(B, 320), "idx2": u8(B, 320), "h1": f(B, 50),
             "m3": u8(B, 50), "d3": f(B, 50), "logp": f(B, 10),
             "glog": f(B, 10), "gh1": f(B, 50), "ga2": f(B, 1280),
-            # partial rows are GW_ROW = 21840 + 7*260 wide (conv1's
-            # 8 weight-grad sub-blocks write disjoint slices;
-            # kernels.hip)
-            "ga1": f(B, 5760), "part": f(32, 23660), "loss": f(()),
+            "ga1": f(B, 5760), "part": f(k.GW_MAX_CH, k.GW_ROW),
             # loss_part must cover the LARGEST forward grid any caller
             # can launch (grid_for(B,1) <= 4096) — sized once here so
             # every entry point shares a safe buffer regardless of
             # which ran first (advisor r1 finding #1)
-            "loss_part": f(4096), "one": torch.ones((), device=device),
+            "loss_part": f(4096), "loss": f(()),
+            "one": torch.ones((), device=device),  # the loss gradient
         }
-        _ws_cache[key] = w
+        object.__setattr__(self, "_tensors", t)
+        object.__setattr__(self, "ptrs",
+                           tuple(t[n].data_ptr() for n in k.ws_fields))
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        return self._tensors[name]
+
+    def __setattr__(self, name, value):
+        raise AttributeError("the fused workspace is read-only")
+
+
+_ws_cache: Dict[Tuple, _Workspace] = {}
+
+
+def _ws(B: int, device) -> _Workspace:
+    key = (B, device.index)
+    w = _ws_cache.get(key)
+    if w is None:
+        w = _ws_cache[key] = _Workspace(load_native("_kernels"), B, device)
     return w
+
+
+def _params(net) -> List[torch.Tensor]:
+    """Net's 8 parameters in kernel order, each with a ``.grad`` to
+    overwrite.  Pointers are read from these on every call: they can
+    move (``attach_flat_grads`` re-points the grads)."""
+    params = [net.conv1.weight, net.conv1.bias, net.conv2.weight,
+              net.conv2.bias, net.fc1.weight, net.fc1.bias,
+              net.fc2.weight, net.fc2.bias]
+    for p in params:
+        if p.grad is None:
+            p.grad = torch.empty_like(p)
+    return params
+
+
+def _ptrs(tensors) -> List[int]:
+    return [t.data_ptr() for t in tensors]
+
+
+def _sgd(opt, params):
+    """(param ptrs, momentum-buffer ptrs, lr, momentum) of the in-kernel
+    FusedSGD update; an empty param list means no update."""
+    if opt is None:
+        return [], [], 0.0, 0.0
+    return (_ptrs(params), _ptrs(opt._bufs) if opt._bufs else [],
+            opt.lr, opt.momentum)
 
 
 def attach_flat_grads(net) -> torch.Tensor:
@@ -76,24 +122,21 @@ def attach_flat_grads(net) -> torch.Tensor:
 
 
 class _NetFusedLoss(torch.autograd.Function):
+    # legacy loss mode (use_loss_part=False): the forward accumulates
+    # the loss scalar atomically, so it is complete before backward
+
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, wf1, bf1, wf2, bf2, tgt, training):
         k = load_native("_kernels")
         B = x.shape[0]
         ws = _ws(B, x.device)
-        k.net_fused_fwd(
-            x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-            b2.data_ptr(), wf1.data_ptr(), bf1.data_ptr(), wf2.data_ptr(),
-            bf2.data_ptr(), tgt.data_ptr(),
-            ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-            ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-            ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-            ws["loss"].data_ptr(), 0, _seed_ptr(x.device), B, training,
-            _stream())
+        params = (w1, b1, w2, b2, wf1, bf1, wf2, bf2)
+        k.net_fused_fwd(x.data_ptr(), _ptrs(params), tgt.data_ptr(),
+                        ws.ptrs, False, _seed_ptr(x.device), B, training,
+                        _stream())
         ctx.save_for_backward(x, w2, wf1, wf2, tgt)
         ctx.meta = (B, training)
-        ctx.shapes = [w1.shape, b1.shape, w2.shape, b2.shape, wf1.shape,
-                      bf1.shape, wf2.shape, bf2.shape]
+        ctx.shapes = [p.shape for p in params]
         return ws["loss"].clone()
 
     @staticmethod
@@ -102,21 +145,32 @@ class _NetFusedLoss(torch.autograd.Function):
         x, w2, wf1, wf2, tgt = ctx.saved_tensors
         B, training = ctx.meta
         ws = _ws(B, x.device)
-        dev = x.device
-        grads = [torch.empty(s, device=dev) for s in ctx.shapes]
+        grads = [torch.empty(s, device=x.device) for s in ctx.shapes]
         gl = gl.contiguous()
-        k.net_fused_bwd(
-            x.data_ptr(), w2.data_ptr(), wf1.data_ptr(), wf2.data_ptr(),
-            tgt.data_ptr(), gl.data_ptr(),
-            ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-            ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-            ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-            ws["glog"].data_ptr(), ws["gh1"].data_ptr(),
-            ws["ga2"].data_ptr(), ws["ga1"].data_ptr(),
-            ws["part"].data_ptr(),
-            *[g.data_ptr() for g in grads], B, training, 0, 0,
-            _seed_ptr(x.device), _stream())
+        k.net_fused_bwd(x.data_ptr(), w2.data_ptr(), wf1.data_ptr(),
+                        wf2.data_ptr(), tgt.data_ptr(), gl.data_ptr(),
+                        ws.ptrs, _ptrs(grads), [], [], 0.0, 0.0, B,
+                        training, False, _seed_ptr(x.device), _stream())
         return (None, *grads, None, None)
+
+
+def _fwd_bwd(net, x, tgt, opt) -> torch.Tensor:
+    # loss_part mode: no prologue dispatch — the forward writes
+    # per-block loss partials (fwd grid <= 4096 at any B); the combine
+    # kernel finalizes the loss scalar and bumps the dropout seed
+    k = load_native("_kernels")
+    B = x.shape[0]
+    ws = _ws(B, x.device)
+    params = _params(net)
+    prm = _ptrs(params)
+    s = _stream()
+    k.net_fused_fwd(x.data_ptr(), prm, tgt.data_ptr(), ws.ptrs, True,
+                    _seed_ptr(x.device), B, net.training, s)
+    k.net_fused_bwd(x.data_ptr(), prm[2], prm[4], prm[6], tgt.data_ptr(),
+                    ws["one"].data_ptr(), ws.ptrs,
+                    _ptrs(p.grad for p in params), *_sgd(opt, params), B,
+                    net.training, True, _seed_ptr(x.device), s)
+    return ws["loss"]
 
 
 def net_fused_step(net, x: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
@@ -124,38 +178,7 @@ def net_fused_step(net, x: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
     ``.grad`` (no autograd graph, no accumulate-add kernels — the
     minimal-launch training step used by bench.py).  Returns the loss
     as a device scalar (no host sync)."""
-    k = load_native("_kernels")
-    B = x.shape[0]
-    ws = _ws(B, x.device)
-    params = [net.conv1.weight, net.conv1.bias, net.conv2.weight,
-              net.conv2.bias, net.fc1.weight, net.fc1.bias,
-              net.fc2.weight, net.fc2.bias]
-    for p in params:
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-    s = _stream()
-    # loss_part mode: no prologue dispatch — the forward writes
-    # per-block loss partials (fwd grid <= 4096 at any B); the combine
-    # kernel finalizes the loss scalar and bumps the dropout seed
-    lp = ws["loss_part"].data_ptr()
-    k.net_fused_fwd(
-        x.data_ptr(), *[p.data_ptr() for p in params], tgt.data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["loss"].data_ptr(), lp, _seed_ptr(x.device), B,
-        net.training, s)
-    k.net_fused_bwd(
-        x.data_ptr(), params[2].data_ptr(), params[4].data_ptr(),
-        params[6].data_ptr(), tgt.data_ptr(), ws["one"].data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["glog"].data_ptr(), ws["gh1"].data_ptr(), ws["ga2"].data_ptr(),
-        ws["ga1"].data_ptr(), ws["part"].data_ptr(),
-        *[p.grad.data_ptr() for p in params], B, net.training,
-        lp, ws["loss"].data_ptr(), _seed_ptr(x.device), s)
-    return ws["loss"]
+    return _fwd_bwd(net, x, tgt, None)
 
 
 def net_fused_step_opt(net, x: torch.Tensor, tgt: torch.Tensor,
@@ -164,37 +187,7 @@ def net_fused_step_opt(net, x: torch.Tensor, tgt: torch.Tensor,
     combine kernel (one dispatch fewer; single-GPU training only — the
     DP path needs the all-reduce between combine and step).  ``opt``
     must be a FusedSGD; its momentum buffers are updated in-kernel."""
-    k = load_native("_kernels")
-    B = x.shape[0]
-    ws = _ws(B, x.device)
-    params = [net.conv1.weight, net.conv1.bias, net.conv2.weight,
-              net.conv2.bias, net.fc1.weight, net.fc1.bias,
-              net.fc2.weight, net.fc2.bias]
-    for p in params:
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-    s = _stream()
-    lp = ws["loss_part"].data_ptr()
-    k.net_fused_fwd(
-        x.data_ptr(), *[p.data_ptr() for p in params], tgt.data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["loss"].data_ptr(), lp, _seed_ptr(x.device), B,
-        net.training, s)
-    bufs = [b.data_ptr() for b in opt._bufs] if opt._bufs else []
-    k.net_fused_bwd_sgd(
-        x.data_ptr(), params[2].data_ptr(), params[4].data_ptr(),
-        params[6].data_ptr(), tgt.data_ptr(), ws["one"].data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["glog"].data_ptr(), ws["gh1"].data_ptr(), ws["ga2"].data_ptr(),
-        ws["ga1"].data_ptr(), ws["part"].data_ptr(),
-        [p.grad.data_ptr() for p in params],
-        [p.data_ptr() for p in params], bufs, opt.lr, opt.momentum, B,
-        net.training, lp, ws["loss"].data_ptr(), _seed_ptr(x.device), s)
-    return ws["loss"]
+    return _fwd_bwd(net, x, tgt, opt)
 
 
 def net_fused_step_fb(net, x: torch.Tensor, tgt: torch.Tensor,
@@ -211,28 +204,10 @@ def net_fused_step_fb(net, x: torch.Tensor, tgt: torch.Tensor,
     k = load_native("_kernels")
     B = x.shape[0]
     ws = _ws(B, x.device)
-    params = [net.conv1.weight, net.conv1.bias, net.conv2.weight,
-              net.conv2.bias, net.fc1.weight, net.fc1.bias,
-              net.fc2.weight, net.fc2.bias]
-    for p in params:
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-    if opt is not None:
-        prm = [p.data_ptr() for p in params]
-        bufs = [b.data_ptr() for b in opt._bufs] if opt._bufs else []
-        lr, mu = opt.lr, opt.momentum
-    else:
-        prm, bufs, lr, mu = [], [], 0.0, 0.0
-    k.net_fused_fwdbwd(
-        x.data_ptr(), *[p.data_ptr() for p in params], tgt.data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["glog"].data_ptr(), ws["gh1"].data_ptr(), ws["ga2"].data_ptr(),
-        ws["ga1"].data_ptr(), ws["part"].data_ptr(),
-        [p.grad.data_ptr() for p in params], prm, bufs, lr, mu, B,
-        net.training, ws["loss_part"].data_ptr(), ws["loss"].data_ptr(),
-        _seed_ptr(x.device), _stream())
+    params = _params(net)
+    k.net_fused_fwdbwd(x.data_ptr(), _ptrs(params), tgt.data_ptr(), ws.ptrs,
+                       _ptrs(p.grad for p in params), *_sgd(opt, params), B,
+                       net.training, _seed_ptr(x.device), _stream())
     return ws["loss"]
 
 
@@ -249,7 +224,7 @@ def net_fused_train_step(net, x: torch.Tensor, tgt: torch.Tensor,
                          opt=None, do_sgd: bool = True) -> torch.Tensor:
     """The WHOLE training step — forward, backward, weight-gradient
     reduction and (optionally) the SGD+momentum update — in ONE
-    cooperative kernel launch (csrc/kernels.hip net_step_kernel).
+    cooperative kernel launch (csrc/net_fused.hip net_step_kernel).
 
     The 6-dispatch fused path pays a ~4.5 us device dispatch floor per
     kernel at the reference's batch sizes; this replaces them with one
@@ -262,29 +237,12 @@ def net_fused_train_step(net, x: torch.Tensor, tgt: torch.Tensor,
     k = load_native("_kernels")
     B = x.shape[0]
     ws = _ws(B, x.device)
-    params = [net.conv1.weight, net.conv1.bias, net.conv2.weight,
-              net.conv2.bias, net.fc1.weight, net.fc1.bias,
-              net.fc2.weight, net.fc2.bias]
-    for p in params:
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-    if do_sgd:
-        lr, mu = opt.lr, opt.momentum
-        bufs = [b.data_ptr() for b in opt._bufs] if opt._bufs else []
-    else:
-        lr, mu, bufs = 0.0, 0.0, []
-    k.net_step(
-        x.data_ptr(), tgt.data_ptr(), ws["one"].data_ptr(),
-        ws["p1"].data_ptr(), ws["idx1"].data_ptr(), ws["m2"].data_ptr(),
-        ws["p2"].data_ptr(), ws["idx2"].data_ptr(), ws["h1"].data_ptr(),
-        ws["m3"].data_ptr(), ws["d3"].data_ptr(), ws["logp"].data_ptr(),
-        ws["glog"].data_ptr(), ws["gh1"].data_ptr(), ws["ga2"].data_ptr(),
-        ws["ga1"].data_ptr(), ws["part"].data_ptr(),
-        ws["loss_part"].data_ptr(), ws["loss"].data_ptr(),
-        _seed_ptr(x.device),
-        [p.data_ptr() for p in params],
-        [p.grad.data_ptr() for p in params],
-        bufs, lr, mu, do_sgd, B, net.training, _stream())
+    params = _params(net)
+    _, bufs, lr, mu = _sgd(opt if do_sgd else None, params)
+    k.net_step(x.data_ptr(), tgt.data_ptr(), ws["one"].data_ptr(), ws.ptrs,
+               _seed_ptr(x.device), _ptrs(params),
+               _ptrs(p.grad for p in params), bufs, lr, mu, do_sgd, B,
+               net.training, _stream())
     return ws["loss"]
 
 

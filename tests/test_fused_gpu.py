@@ -299,47 +299,109 @@ def test_fwdbwd_training_convergence():
     assert last < first - 0.12, (first, last)
 
 
-def test_fold_optin_matches_default_subprocess():
+def _one_step_state(kind):
+    """One eval-mode training step at B=64 through entry point `kind`;
+    returns grads, parameters and momentum buffers as flat lists.
+    Self-contained: its source also runs in the fold subprocess."""
+    import torch
+    from dist_tuto_pth_amd.models import Net
+    from dist_tuto_pth_amd.ops import fused
+    from dist_tuto_pth_amd.optim import FusedSGD
+    torch.manual_seed(11)
+    net_c = Net().eval()
+    net_g = Net().eval().to("cuda:0")
+    net_g.load_state_dict({k: v.to("cuda:0")
+                           for k, v in net_c.state_dict().items()})
+    x = torch.randn(64, 1, 28, 28).to("cuda:0")
+    tgt = torch.randint(0, 10, (64,)).to("cuda:0")
+    bufs = []
+    if kind == "step":
+        fused.net_fused_step(net_g, x, tgt)
+    else:
+        opt = FusedSGD(net_g.parameters(), lr=0.01, momentum=0.5)
+        step = {"opt": fused.net_fused_step_opt,
+                "fb": fused.net_fused_step_fb}[kind]
+        step(net_g, x, tgt, opt)
+        bufs = opt._bufs
+    torch.cuda.synchronize()
+    out = {}
+    for n, p in net_g.named_parameters():
+        out["grad " + n] = p.grad.cpu().flatten().tolist()
+        out["param " + n] = p.detach().cpu().flatten().tolist()
+    for i, b in enumerate(bufs):
+        out["momentum %d" % i] = b.cpu().flatten().tolist()
+    return out
+
+
+@pytest.mark.parametrize("kind", ["step", "opt", "fb"])
+def test_fold_optin_matches_default_subprocess(kind):
     """The opt-in in-launch gw fold (DTP_GW_FOLD=1, a documented
     measured-negative kept for the record — see
-    profiles/convnet_step_history.md) must stay numerically correct:
-    run one fused step in a subprocess with the flag set (it is read
-    once per process) and compare grads against this process's
-    default combine path."""
+    profiles/convnet_step_history.md) must stay numerically correct at
+    every call site of the gw launch: run one step (plain, with the
+    fused optimizer, and through the combined fwd+bwd kernel with the
+    fused optimizer) in a subprocess with the flag set (it is read once
+    per process) and compare grads, updated parameters and momentum
+    buffers against this process's default combine path."""
+    import inspect
     import json
     import os
     import subprocess
     import sys
 
-    net_c, net_g, x, tgt = _mk(11)
-    net_fused_step(net_g, x.to(DEV), tgt.to(DEV))
-    torch.cuda.synchronize()
-    want = {n: p.grad.cpu() for n, p in net_g.named_parameters()}
+    want = _one_step_state(kind)
+    assert len(want) == (16 if kind == "step" else 24)
 
-    prog = (
-        "import json, sys, torch\n"
-        "from dist_tuto_pth_amd.models import Net\n"
-        "from dist_tuto_pth_amd.ops.fused import net_fused_step\n"
-        "torch.manual_seed(11)\n"
-        "net_c = Net().eval(); net_g = Net().eval().to('cuda:0')\n"
-        "net_g.load_state_dict({k: v.to('cuda:0')\n"
-        "                       for k, v in net_c.state_dict().items()})\n"
-        "x = torch.randn(64, 1, 28, 28); tgt = torch.randint(0, 10, (64,))\n"
-        "net_fused_step(net_g, x.to('cuda:0'), tgt.to('cuda:0'))\n"
-        "torch.cuda.synchronize()\n"
-        "out = {n: p.grad.cpu().flatten().tolist()\n"
-        "       for n, p in net_g.named_parameters()}\n"
-        "print(json.dumps(out))\n"
-    )
+    prog = (inspect.getsource(_one_step_state) +
+            "\nimport json, sys\n"
+            "print(json.dumps(_one_step_state(sys.argv[1])))\n")
     env = dict(os.environ, DTP_GW_FOLD="1")
-    r = subprocess.run([sys.executable, "-c", prog], env=env,
+    r = subprocess.run([sys.executable, "-c", prog, kind], env=env,
                        capture_output=True, text=True, timeout=180)
     assert r.returncode == 0, r.stderr[-2000:]
     got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert got.keys() == want.keys()
     for n, w in want.items():
-        g = torch.tensor(got[n]).view_as(w)
+        g, w = torch.tensor(got[n]), torch.tensor(w)
         assert torch.allclose(g, w, atol=1e-6), \
             (n, (g - w).abs().max().item())
+
+
+@pytest.mark.parametrize("B", [6, 193])
+def test_interleaved_entry_points_share_workspace(B):
+    """Every entry point runs on the ONE cached per-(B, device)
+    workspace and pointer vector: calling them in turn on one net (eval
+    mode) must give the same loss and gradients each time.  B=6 is below
+    every gw chunk count (nch = B) and takes the split forward; B=193
+    has no split, nch=24 / nch2=32 and chunks that do not divide B."""
+    from dist_tuto_pth_amd.ops.fused import (net_fused_step_fb,
+                                             net_fused_train_step,
+                                             net_step_available)
+    _, net_g, x, tgt = _mk(30 + B, B=B)
+    xg, tg = x.to(DEV), tgt.to(DEV)
+    params = list(net_g.named_parameters())
+
+    loss0 = net_fused_loss(net_g, xg, tg)
+    loss0.backward()
+    torch.cuda.synchronize()
+    loss0 = loss0.detach().clone()
+    want = [p.grad.clone() for _, p in params]
+    assert all(w.abs().sum() > 0 for w in want)
+
+    steps = [("step", lambda: net_fused_step(net_g, xg, tg)),
+             ("fb", lambda: net_fused_step_fb(net_g, xg, tg))]
+    if net_step_available():
+        steps.append(("train_step", lambda: net_fused_train_step(
+            net_g, xg, tg, do_sgd=False)))
+    for name, step in steps:
+        loss = step().clone()
+        torch.cuda.synchronize()
+        assert torch.allclose(loss, loss0, atol=1e-6), \
+            (name, loss.item(), loss0.item())
+        for (n, p), w in zip(params, want):
+            assert torch.allclose(p.grad, w, atol=1e-6), \
+                (name, n, (p.grad - w).abs().max().item())
+            p.grad.zero_()  # the next entry point must rewrite it
 
 
 @pytest.mark.parametrize("B", [33, 100, 257])

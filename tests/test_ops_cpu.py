@@ -155,3 +155,32 @@ def test_net_step_available_false_on_cpu():
     import torch
     if not torch.cuda.is_available():
         assert net_step_available() is False
+
+
+def test_gw_chunk_plan_and_exported_constants():
+    """The weight-gradient chunk policy and the partial-row layout are
+    defined once, in the native module; Python sizes the workspace and
+    the microbenchmarks launch raw segments from these exports."""
+    import os
+    import pytest
+    from dist_tuto_pth_amd.utils.native import load_native
+    for v in ("DTP_GW_NCH", "DTP_GW_NCH1", "DTP_GW_NCH2", "DTP_GW_FOLD"):
+        if v in os.environ:
+            pytest.skip(f"{v} overrides the default chunk plan")
+    k = load_native("_kernels")
+    assert k.GW_TOTAL == 21840
+    assert k.GW_ROW == 21840 + 7 * 260
+    assert k.GW_MAX_CH == 32
+    assert k.gw_tiles == (("conv2", 8), ("conv1", 8), ("fc1", 63),
+                          ("fc2", 2))
+    assert k.ws_fields == ("p1", "idx1", "m2", "p2", "idx2", "h1", "m3",
+                           "d3", "logp", "glog", "gh1", "ga2", "ga1",
+                           "part", "loss_part", "loss")
+    want = {128: (16, 16, 24), 192: (16, 16, 24), 193: (24, 24, 32),
+            4096: (24, 24, 32), 5: (5, 5, 5), 1: (1, 1, 1)}
+    for B, nchs in want.items():
+        pl = k.gw_plan(B)
+        assert (pl["nch"], pl["nch1"], pl["nch2"]) == nchs, (B, pl)
+        for fam in ("", "1", "2"):
+            assert pl["bchunk" + fam] == -(-B // pl["nch" + fam]), (B, pl)
+        assert pl["gy"] == max(nchs)
