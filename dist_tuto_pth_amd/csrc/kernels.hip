@@ -14,8 +14,9 @@
 // Build: hipcc --offload-arch=gfx950 (build.py).  No CUDA paths.
 //
 // This file also owns PYBIND11_MODULE; the fused whole-Net step
-// (net_fused.hip) and the bf16 linear (linear_bf16.hip) register their
-// bindings through register_net_fused() / register_linear_bf16().
+// (net_fused.hip), the bf16 linear (linear_bf16.hip) and the bf16
+// convolution (conv_bf16.hip) register their bindings through
+// register_net_fused() / register_linear_bf16() / register_conv_bf16().
 
 #include "common.h"
 
@@ -1053,9 +1054,11 @@ void launch_bump_seed(uintptr_t seed_ptr, hipStream_t stream) {
 }
 
 // the fused whole-Net step lives in net_fused.hip, K16 (bf16 MFMA
-// linear, bf16 dropout) in linear_bf16.hip
+// linear, bf16 dropout) in linear_bf16.hip, K17 (bf16 MFMA convolution,
+// bf16 maxpool+ReLU and channel dropout) in conv_bf16.hip
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
+void register_conv_bf16(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
@@ -1084,4 +1087,5 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("scale_f32", &scale_f32);
   register_net_fused(m);
   register_linear_bf16(m);
+  register_conv_bf16(m);
 }

@@ -9,6 +9,8 @@ HIP kernel here (``csrc/kernels.hip``), with forward *and* backward:
   K5/K6  dropout2d (channel) / dropout     -> dropout2d / dropout
   K7/K8  linear (+fused ReLU epilogue)     -> linear
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
+  K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
+         bf16 pool+ReLU / channel dropout   -> maxpool2d_relu / dropout2d
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
   K11-13 fused multi-tensor SGD+momentum   -> optim.FusedSGD
@@ -99,8 +101,10 @@ class _MaxPool2dRelu(torch.autograd.Function):
             out = torch.empty(B, C, OH, OW, device=x.device, dtype=x.dtype)
             idx = torch.empty(B, C, OH, OW, device=x.device,
                               dtype=torch.int32)
-            k.maxpool2d_relu_fwd(x.data_ptr(), out.data_ptr(),
-                                 idx.data_ptr(), B, C, H, W, _stream())
+            fwd = k.maxpool2d_relu_bf16_fwd if x.dtype == torch.bfloat16 \
+                else k.maxpool2d_relu_fwd
+            fwd(_aligned4(x).data_ptr(), out.data_ptr(), idx.data_ptr(),
+                B, C, H, W, _stream())
             ctx.save_for_backward(idx)
             ctx.in_shape = x.shape
             return out
@@ -119,15 +123,37 @@ class _MaxPool2dRelu(torch.autograd.Function):
             B, C, H, W = ctx.in_shape
             gx = torch.empty(ctx.in_shape, device=gy.device,
                              dtype=gy.dtype)  # kernel writes all slots
-            k.maxpool2d_relu_bwd(gy.data_ptr(), idx.data_ptr(),
-                                 gx.data_ptr(), B, C, H, W, _stream())
+            bwd = k.maxpool2d_relu_bf16_bwd if gy.dtype == torch.bfloat16 \
+                else k.maxpool2d_relu_bwd
+            bwd(gy.data_ptr(), idx.data_ptr(), gx.data_ptr(), B, C, H, W,
+                _stream())
             return gx
         idx, pooled = ctx.saved_tensors
         gy = gy * (pooled > 0)
         return F.max_unpool2d(gy, idx, 2, output_size=ctx.in_shape[-2:])
 
 
+def _aligned4(t):
+    """The bf16 pool kernels move 2 elements per access."""
+    return t if t.data_ptr() % 4 == 0 else t.clone()
+
+
 def maxpool2d_relu(x):
+    """``relu(max_pool2d(x, 2))`` on fp32 or bf16 tensors.  Max and ReLU
+    only select values, so the bf16 result is the fp32 op's on the same
+    values, bit for bit; the saved index encoding is shared.  The bf16
+    GPU path requires even ``H`` and ``W``."""
+    if x.is_cuda:
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"ops.maxpool2d_relu: fp32 or bf16 CUDA tensors "
+                            f"only, got {x.dtype}")
+        if x.dtype == torch.bfloat16:
+            if x.dim() != 4:
+                raise ValueError("ops.maxpool2d_relu: [B,C,H,W] expected")
+            if x.shape[2] % 2 or x.shape[3] % 2 or min(x.shape[2:]) < 2:
+                raise ValueError(
+                    f"ops.maxpool2d_relu (bf16): H and W must be even, got "
+                    f"{tuple(x.shape[2:])}")
     return _MaxPool2dRelu.apply(x.contiguous())
 
 
@@ -194,9 +220,10 @@ class _Dropout(torch.autograd.Function):
                 hw = x.numel() // (B * C)
                 mask = torch.empty(B * C, device=x.device,
                                    dtype=torch.uint8)
-                k.dropout2d_fwd(x.data_ptr(), out.data_ptr(),
-                                mask.data_ptr(), B * C, hw, p,
-                                _seed_ptr(x.device), _stream())
+                fwd = k.dropout2d_bf16_fwd if x.dtype == torch.bfloat16 \
+                    else k.dropout2d_fwd
+                fwd(x.data_ptr(), out.data_ptr(), mask.data_ptr(), B * C,
+                    hw, p, _seed_ptr(x.device), _stream())
             else:
                 mask = torch.empty(x.numel(), device=x.device,
                                    dtype=torch.uint8)
@@ -234,8 +261,10 @@ class _Dropout(torch.autograd.Function):
             if channelwise:
                 B, C = shape[0], shape[1]
                 hw = gy.numel() // (B * C)
-                k.dropout2d_bwd(gy.data_ptr(), mask.data_ptr(),
-                                gx.data_ptr(), B * C, hw, scale, _stream())
+                bwd = k.dropout2d_bf16_bwd if gy.dtype == torch.bfloat16 \
+                    else k.dropout2d_bwd
+                bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(), B * C,
+                    hw, scale, _stream())
             else:
                 bwd = k.dropout_bf16_bwd if gy.dtype == torch.bfloat16 \
                     else k.dropout_bwd
@@ -262,6 +291,13 @@ def dropout(x, p=0.5, training=True):
 
 
 def dropout2d(x, p=0.5, training=True):
+    """Channel dropout on fp32 or bf16 tensors.  The bf16 kernels hash the
+    same plane index with the same device-side seed as the fp32 ones, so
+    for equal seed and ``p`` the channel mask is identical; kept values
+    are ``bf16(float(x) * scale)``."""
+    if x.is_cuda and x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(
+            f"ops.dropout2d: fp32 or bf16 CUDA tensors only, got {x.dtype}")
     return _Dropout.apply(x.contiguous(), p, training, True)
 
 
@@ -451,6 +487,171 @@ def linear_bf16(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
             raise ValueError("linear_bf16: b must have shape [N]")
         b = b.contiguous()
     return _LinearBf16.apply(x, w, b, fuse_relu, out_dtype)
+
+
+# ---------------------------------------------------------------------------
+# K17 — mixed-precision convolution: the three products of a conv layer as
+# implicit GEMMs on the bf16 matrix-core tile of linear_bf16, behind
+# im2col loaders (csrc/conv_bf16.hip).  Same contract as linear_bf16, on
+# GPU and CPU alike: bf16 operands (fp32 inputs are rounded RNE first),
+# fp32 accumulation, one rounding per result; padding adds exact zeros.
+# ---------------------------------------------------------------------------
+_CONV_DIM_MAX = 2 ** 31 - 1 - 128   # the kernel's int GEMM dimensions
+
+
+def _pair(v, name, low):
+    if isinstance(v, bool):
+        raise ValueError(f"conv2d_bf16: {name} must be an int or a pair")
+    if isinstance(v, int):
+        v = (v, v)
+    else:
+        try:
+            v = tuple(v)
+        except TypeError:
+            raise ValueError(
+                f"conv2d_bf16: {name} must be an int or a pair") from None
+    if len(v) != 2 or not all(isinstance(e, int) and not isinstance(e, bool)
+                              for e in v):
+        raise ValueError(f"conv2d_bf16: {name} must be an int or a pair of "
+                         f"ints, got {v}")
+    if min(v) < low:
+        raise ValueError(f"conv2d_bf16: {name} must be >= {low}, got {v}")
+    return v
+
+
+class _Conv2dBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, stride, padding, out_dtype):
+        xb, wb = _to_bf16(x), _to_bf16(w)
+        B, C, H, W = xb.shape
+        K, _, R, S = wb.shape
+        (sh, sw), (ph, pw) = stride, padding
+        OH = (H + 2 * ph - R) // sh + 1
+        OW = (W + 2 * pw - S) // sw + 1
+        if x.is_cuda:
+            out = torch.empty(B, K, OH, OW, device=x.device, dtype=out_dtype)
+            _k().conv2d_bf16_fwd(
+                xb.data_ptr(), wb.data_ptr(),
+                b.data_ptr() if b is not None else 0, out.data_ptr(),
+                B, C, H, W, K, R, S, sh, sw, ph, pw,
+                out_dtype == torch.float32, _stream())
+        else:
+            out = F.conv2d(xb.float(), wb.float(), b, stride,
+                           padding).to(out_dtype)
+        ctx.save_for_backward(xb, wb)
+        ctx.geom = (stride, padding, OH, OW)
+        ctx.x_dtype, ctx.w_dtype = x.dtype, w.dtype
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        xb, wb = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        B, C, H, W = xb.shape
+        K, _, R, S = wb.shape
+        stride, padding, OH, OW = ctx.geom
+        (sh, sw), (ph, pw) = stride, padding
+        gyb = _to_bf16(gy)
+        gx = gw = gb = None
+        if xb.is_cuda:
+            k = _k()
+            dims = (B, C, H, W, K, R, S, sh, sw, ph, pw)
+            if need_x:
+                gx = torch.empty(B, C, H, W, device=xb.device,
+                                 dtype=ctx.x_dtype)  # fully written
+                k.conv2d_bf16_bwd_x(gyb.data_ptr(), wb.data_ptr(),
+                                    gx.data_ptr(), *dims,
+                                    ctx.x_dtype == torch.float32, _stream())
+            if need_w or need_b:
+                n_gw = K * C * R * S
+                gw = torch.empty(K, C, R, S, device=xb.device,
+                                 dtype=torch.float32)
+                gb = torch.empty(K, device=xb.device, dtype=torch.float32) \
+                    if need_b else None
+                splits = k.conv2d_bf16_gw_splits(*dims)
+                part = torch.empty(splits * (n_gw + K), device=xb.device,
+                                   dtype=torch.float32) \
+                    if splits > 1 else None
+                k.conv2d_bf16_bwd_w(
+                    gyb.data_ptr(), xb.data_ptr(), gw.data_ptr(),
+                    gb.data_ptr() if gb is not None else 0,
+                    part.data_ptr() if part is not None else 0, splits,
+                    *dims, _stream())
+                if ctx.w_dtype == torch.bfloat16:
+                    gw = _to_bf16(gw)
+                if not need_w:
+                    gw = None
+            return gx, gw, gb, None, None, None
+        g = gyb.float()
+        if need_x:
+            gx = torch.nn.grad.conv2d_input(
+                xb.shape, wb.float(), g, stride, padding).to(ctx.x_dtype)
+        if need_w:
+            gw = torch.nn.grad.conv2d_weight(
+                xb.float(), wb.shape, g, stride, padding).to(ctx.w_dtype)
+        if need_b:
+            gb = g.sum(dim=(0, 2, 3))
+        return gx, gw, gb, None, None, None
+
+
+def conv2d_bf16(x, w, b=None, stride=1, padding=0,
+                out_dtype=torch.bfloat16):
+    """2-D convolution (cross-correlation, NCHW) with bf16 operands and
+    fp32 accumulation.
+
+    ``x`` [B,C,H,W] and ``w`` [K,C,R,S] are fp32 or bf16, ``b`` is fp32 [K]
+    or None; ``stride`` (>= 1) and zero ``padding`` (>= 0) are ints or
+    (h, w) pairs.  The result is [B,K,OH,OW] in ``out_dtype`` (bf16 or
+    fp32) with ``OH = (H + 2*ph - R)//sh + 1``.  No dilation, groups or
+    fused activation.  Backward gives ``gx`` in ``x``'s dtype (exact zeros
+    where no output reads the input), ``gb`` in fp32 and ``gw`` in fp32
+    for an fp32 (master) weight, or rounded once to bf16 for a bf16
+    weight; ``gw`` and ``gb`` are bitwise reproducible."""
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"conv2d_bf16: out_dtype must be torch.bfloat16 or "
+                        f"torch.float32, got {out_dtype}")
+    for name, t in (("x", x), ("w", w)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"conv2d_bf16: {name} must be fp32 or bf16, "
+                            f"got {t.dtype}")
+    if b is not None and b.dtype != torch.float32:
+        raise TypeError(f"conv2d_bf16: b must be fp32, got {b.dtype}")
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(f"conv2d_bf16: x [B,C,H,W] and w [K,C,R,S] expected,"
+                         f" got {tuple(x.shape)} and {tuple(w.shape)}")
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"conv2d_bf16: x has {x.shape[1]} channels, w "
+                         f"expects {w.shape[1]} (groups are not supported)")
+    if min(x.shape) < 1 or min(w.shape) < 1:
+        raise ValueError("conv2d_bf16: every dimension must be >= 1")
+    if b is not None:
+        if b.shape != (w.shape[0],):
+            raise ValueError("conv2d_bf16: b must have shape [K]")
+        b = b.contiguous()
+    sh, sw = _pair(stride, "stride", 1)
+    ph, pw = _pair(padding, "padding", 0)
+    B, C, H, W = x.shape
+    K, _, R, S = w.shape
+    OH = (H + 2 * ph - R) // sh + 1
+    OW = (W + 2 * pw - S) // sw + 1
+    if H + 2 * ph < R or W + 2 * pw < S or OH < 1 or OW < 1:
+        raise ValueError(
+            f"conv2d_bf16: a {R}x{S} filter does not fit the padded "
+            f"{H + 2 * ph}x{W + 2 * pw} input")
+    for what, v in (("B*OH*OW", B * OH * OW), ("B*H*W", B * H * W),
+                    ("C*R*S", C * R * S), ("K*R*S", K * R * S),
+                    ("H+2*ph", H + 2 * ph), ("W+2*pw", W + 2 * pw)):
+        if v > _CONV_DIM_MAX:
+            raise ValueError(
+                f"conv2d_bf16: {what} = {v} does not fit the kernel's "
+                f"32-bit GEMM index")
+    for what, v in (("x", B * C * H * W), ("w", K * C * R * S),
+                    ("out", B * K * OH * OW)):
+        if v >= 2 ** 62:
+            raise ValueError(f"conv2d_bf16: {what} has too many elements")
+    return _Conv2dBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
 
 
 # ---------------------------------------------------------------------------

@@ -79,6 +79,17 @@ def _ws(B: int, device) -> _Workspace:
     return w
 
 
+def _reject_bf16(net, entry: str) -> None:
+    """The fused kernels are fp32 only; a bf16-mode Net must not run them
+    silently in fp32.  Every entry point checks ``compute_dtype`` inline
+    (one attribute read per step) and comes here to raise."""
+    raise TypeError(
+        f"{entry}: the fused whole-Net kernels are fp32 only, but this Net "
+        f"has compute_dtype={net.compute_dtype}; use the modular path "
+        f"(net.forward_logits + ops.log_softmax_nll) or build the Net with "
+        f"compute_dtype=None")
+
+
 def _params(net) -> List[torch.Tensor]:
     """Net's 8 parameters in kernel order, each with a ``.grad`` to
     overwrite.  Pointers are read from these on every call: they can
@@ -178,6 +189,8 @@ def net_fused_step(net, x: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
     ``.grad`` (no autograd graph, no accumulate-add kernels — the
     minimal-launch training step used by bench.py).  Returns the loss
     as a device scalar (no host sync)."""
+    if getattr(net, "compute_dtype", None) is not None:
+        _reject_bf16(net, "net_fused_step")
     return _fwd_bwd(net, x, tgt, None)
 
 
@@ -187,6 +200,8 @@ def net_fused_step_opt(net, x: torch.Tensor, tgt: torch.Tensor,
     combine kernel (one dispatch fewer; single-GPU training only — the
     DP path needs the all-reduce between combine and step).  ``opt``
     must be a FusedSGD; its momentum buffers are updated in-kernel."""
+    if getattr(net, "compute_dtype", None) is not None:
+        _reject_bf16(net, "net_fused_step_opt")
     return _fwd_bwd(net, x, tgt, opt)
 
 
@@ -201,6 +216,8 @@ def net_fused_step_fb(net, x: torch.Tensor, tgt: torch.Tensor,
     net_fused_step: one dispatch + w2 re-staging saved, but the
     backward loses its sibling-workgroup split (grid = B), so at small
     B the chip is underfilled — measured, see profiles/."""
+    if getattr(net, "compute_dtype", None) is not None:
+        _reject_bf16(net, "net_fused_step_fb")
     k = load_native("_kernels")
     B = x.shape[0]
     ws = _ws(B, x.device)
@@ -234,6 +251,8 @@ def net_fused_train_step(net, x: torch.Tensor, tgt: torch.Tensor,
     its momentum buffers are updated in-kernel.  Returns the loss as a
     device scalar (no host sync).
     """
+    if getattr(net, "compute_dtype", None) is not None:
+        _reject_bf16(net, "net_fused_train_step")
     k = load_native("_kernels")
     B = x.shape[0]
     ws = _ws(B, x.device)
@@ -249,6 +268,8 @@ def net_fused_train_step(net, x: torch.Tensor, tgt: torch.Tensor,
 def net_fused_loss(net, x: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
     """Mean NLL loss of ``net`` (a models.Net) on (x, tgt), computed by
     the fused kernels.  Gradients flow to the 8 parameters."""
+    if getattr(net, "compute_dtype", None) is not None:
+        _reject_bf16(net, "net_fused_loss")
     assert x.is_cuda, "fused path is the GPU fast path"
     return _NetFusedLoss.apply(
         x.contiguous(), net.conv1.weight, net.conv1.bias,
