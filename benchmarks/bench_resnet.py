@@ -45,7 +45,15 @@ def main():
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                    help="bf16 = autocast compute (supplementary number; "
                         "the headline config is fp32)")
+    p.add_argument("--compute-dtype", default=None, choices=["bf16"],
+                   help="build the model with compute_dtype=bfloat16: "
+                        "convs, BN and the classifier on this package's "
+                        "own HIP ops; autocast and channels_last are off")
     args = p.parse_args()
+    own_bf16 = args.compute_dtype == "bf16"
+    if own_bf16:
+        args.channels_last = False
+        args.dtype = "fp32"      # no autocast: the model casts itself
 
     # MIOpen exhaustive find: pick the fastest conv kernel per shape
     # during warmup (the warmup steps absorb the search cost)
@@ -64,7 +72,8 @@ def main():
     device = f"cuda:{dev_idx}"
 
     torch.manual_seed(1234)
-    model = resnet50().to(device)
+    model = (resnet50(compute_dtype=torch.bfloat16) if own_bf16
+             else resnet50()).to(device)
     if args.channels_last:
         model = model.to(memory_format=torch.channels_last)
     if world > 1:
@@ -134,7 +143,8 @@ def main():
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
-            "dtype": args.dtype,
+            "dtype": "bf16 (compute_dtype, own HIP ops)" if own_bf16
+            else args.dtype,
             "data": "synthetic",
             "config": {"model": "ResNet-50", "global_batch":
                        args.batch * world, "input": "3x224x224",

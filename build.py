@@ -49,7 +49,8 @@ def build(force: bool = False):
         # (output, sources, headers, extra flags)
         ("_rcclx.so", src("rcclx.cpp"), [], ["-L/opt/rocm/lib", "-lrccl"]),
         ("_kernels.so", src("kernels.hip", "net_fused.hip",
-                            "linear_bf16.hip", "conv_bf16.hip"),
+                            "linear_bf16.hip", "conv_bf16.hip",
+                            "batchnorm.hip"),
          src("common.h", "gemm_bf16.h"), []),
     ]
     for out_name, srcs, hdrs, extra in targets:

@@ -14,9 +14,10 @@
 // Build: hipcc --offload-arch=gfx950 (build.py).  No CUDA paths.
 //
 // This file also owns PYBIND11_MODULE; the fused whole-Net step
-// (net_fused.hip), the bf16 linear (linear_bf16.hip) and the bf16
-// convolution (conv_bf16.hip) register their bindings through
-// register_net_fused() / register_linear_bf16() / register_conv_bf16().
+// (net_fused.hip), the bf16 linear (linear_bf16.hip), the bf16
+// convolution (conv_bf16.hip) and batch normalization (batchnorm.hip)
+// register their bindings through register_net_fused() /
+// register_linear_bf16() / register_conv_bf16() / register_batchnorm().
 
 #include "common.h"
 
@@ -1055,10 +1056,12 @@ void launch_bump_seed(uintptr_t seed_ptr, hipStream_t stream) {
 
 // the fused whole-Net step lives in net_fused.hip, K16 (bf16 MFMA
 // linear, bf16 dropout) in linear_bf16.hip, K17 (bf16 MFMA convolution,
-// bf16 maxpool+ReLU and channel dropout) in conv_bf16.hip
+// bf16 maxpool+ReLU and channel dropout) in conv_bf16.hip, K18 (batch
+// normalization with fused add and ReLU) in batchnorm.hip
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
+void register_batchnorm(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
@@ -1088,4 +1091,5 @@ PYBIND11_MODULE(_kernels, m) {
   register_net_fused(m);
   register_linear_bf16(m);
   register_conv_bf16(m);
+  register_batchnorm(m);
 }

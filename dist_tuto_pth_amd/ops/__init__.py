@@ -11,6 +11,7 @@ HIP kernel here (``csrc/kernels.hip``), with forward *and* backward:
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
          bf16 pool+ReLU / channel dropout   -> maxpool2d_relu / dropout2d
+  K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
   K11-13 fused multi-tensor SGD+momentum   -> optim.FusedSGD
@@ -652,6 +653,222 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
         if v >= 2 ** 62:
             raise ValueError(f"conv2d_bf16: {what} has too many elements")
     return _Conv2dBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
+
+
+# ---------------------------------------------------------------------------
+# K18 — batch normalization over NCHW, fp32 or bf16 activations, with an
+# optional residual add and ReLU fused into the same pass
+# (csrc/batchnorm.hip).  Contract, on GPU and CPU alike: statistics and all
+# arithmetic are fp32, the variance is the centred second moment (never
+# E[x^2] - E[x]^2), each output element is rounded once to its dtype, and
+# nothing uses float atomics, so every result is bitwise reproducible.
+# ---------------------------------------------------------------------------
+_BN_MAX_ELEMS = 2 ** 31 - 1   # the kernels' 32-bit access indices
+
+
+def _bn_chan(t):
+    return t.view(1, -1, 1, 1)
+
+
+def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
+                         training, momentum, eps, residual, fuse_relu):
+    """The forward of ``batchnorm2d`` on checked, contiguous tensors.
+    Returns ``(y, save_mean, save_invstd)``: the fp32 batch statistics the
+    backward uses in training, ``(y, None, None)`` in eval."""
+    B, C, H, W = x.shape
+    if x.is_cuda:
+        k = _k()
+        y = torch.empty_like(x)
+        mean = invstd = ws = None
+        splits = 1
+        if training:
+            mean = torch.empty(C, device=x.device, dtype=torch.float32)
+            invstd = torch.empty(C, device=x.device, dtype=torch.float32)
+            splits = k.batchnorm2d_splits(B, C, H * W)
+            ws = torch.empty(C * splits * 3, device=x.device,
+                             dtype=torch.float32)
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        k.batchnorm2d_fwd(
+            x.data_ptr(), ptr(residual), y.data_ptr(), weight.data_ptr(),
+            bias.data_ptr(), ptr(running_mean), ptr(running_var), ptr(mean),
+            ptr(invstd), ptr(ws), splits, B, C, H * W, training, momentum,
+            eps, fuse_relu, x.dtype == torch.bfloat16, _stream())
+        return y, mean, invstd
+    xf = x.float()
+    if training:
+        n = B * H * W
+        mean = xf.mean(dim=(0, 2, 3))
+        d = xf - _bn_chan(mean)
+        var = (d * d).mean(dim=(0, 2, 3))
+        invstd = 1.0 / torch.sqrt(var + eps)
+        if running_mean is not None:
+            running_mean.mul_(1.0 - momentum).add_(mean, alpha=momentum)
+            running_var.mul_(1.0 - momentum).add_(var * (n / (n - 1.0)),
+                                                  alpha=momentum)
+        mu, inv = mean, invstd
+    else:
+        mean = invstd = None
+        mu, inv = running_mean, 1.0 / torch.sqrt(running_var + eps)
+    yf = (xf - _bn_chan(mu)) * _bn_chan(weight * inv) + _bn_chan(bias)
+    if residual is not None:
+        yf = yf + residual.float()
+    if fuse_relu:
+        yf = F.relu(yf)
+    return yf.to(x.dtype), mean, invstd
+
+
+class _BatchNorm2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var,
+                training, momentum, eps, fuse_relu):
+        y, mean, invstd = _batchnorm2d_forward(
+            x, weight, bias, running_mean, running_var, training, momentum,
+            eps, residual, fuse_relu)
+        if training:
+            ctx.save_for_backward(x, weight, mean, invstd,
+                                  y if fuse_relu else None)
+        else:
+            ctx.save_for_backward(x, weight, running_mean, running_var,
+                                  y if fuse_relu else None)
+        ctx.training, ctx.eps = training, eps
+        ctx.has_residual = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, mean, stat, y = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        need_r = need_r and ctx.has_residual
+        B, C, H, W = x.shape
+        n = B * H * W
+        gy = gy.contiguous()
+        gx = gres = None
+        if x.is_cuda:
+            k = _k()
+            gw = torch.empty(C, device=x.device, dtype=torch.float32)
+            gb = torch.empty(C, device=x.device, dtype=torch.float32)
+            if need_x:
+                gx = torch.empty_like(x)     # fully written
+            if need_r:
+                gres = torch.empty_like(x)
+            splits = k.batchnorm2d_splits(B, C, H * W)
+            ws = torch.empty(C * splits * 2, device=x.device,
+                             dtype=torch.float32)
+            k.batchnorm2d_bwd(
+                x.data_ptr(), gy.data_ptr(),
+                y.data_ptr() if y is not None else 0, weight.data_ptr(),
+                mean.data_ptr(), stat.data_ptr(), gw.data_ptr(),
+                gb.data_ptr(), gx.data_ptr() if gx is not None else 0,
+                gres.data_ptr() if gres is not None else 0, ws.data_ptr(),
+                splits, B, C, H * W, ctx.training, ctx.eps,
+                x.dtype == torch.bfloat16, _stream())
+        else:
+            inv = stat if ctx.training else 1.0 / torch.sqrt(stat + ctx.eps)
+            g = gy.float()
+            if y is not None:
+                g = g * (y > 0)
+            xhat = (x.float() - _bn_chan(mean)) * _bn_chan(inv)
+            gb = g.sum(dim=(0, 2, 3))
+            gw = (g * xhat).sum(dim=(0, 2, 3))
+            if need_x:
+                if ctx.training:
+                    t = g - _bn_chan(gb / n) - xhat * _bn_chan(gw / n)
+                else:
+                    t = g
+                gx = (_bn_chan(weight * inv) * t).to(x.dtype)
+            if need_r:
+                gres = g.to(x.dtype)
+        return (gx, gw if need_w else None, gb if need_b else None, gres,
+                None, None, None, None, None, None)
+
+
+def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
+                training=True, momentum=0.1, eps=1e-5, residual=None,
+                fuse_relu=False):
+    """``relu?(batch_norm(x) + residual?)`` over NCHW in one pass.
+
+    ``x`` [B,C,H,W] is fp32 or bf16 and the result has its dtype and shape;
+    ``residual``, when given, has both too.  ``weight``, ``bias`` and the
+    running buffers are fp32 [C].  ``training=True`` normalizes with the
+    batch statistics (biased variance) and, when running buffers are
+    given, updates them in place on the stream —
+    ``rm = (1-m)*rm + m*mean``, ``rv = (1-m)*rv + m*var*n/(n-1)`` — so the
+    update survives graph replay; ``training=False`` normalizes with the
+    running buffers and leaves them alone.  ``momentum=None`` (torch's
+    cumulative average) is not supported.  Backward gives ``gx`` in ``x``'s
+    dtype, the residual's gradient in its dtype (the gradient after the
+    ReLU mask, exactly) and fp32 ``gweight``/``gbias``.  Statistics and
+    arithmetic are fp32 with a centred variance and one rounding per
+    element; every output is bitwise reproducible."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ops.batchnorm2d: x must be fp32 or bf16, got "
+                        f"{x.dtype}")
+    if x.dim() != 4:
+        raise ValueError(f"ops.batchnorm2d: x [B,C,H,W] expected, got "
+                         f"{tuple(x.shape)}")
+    if min(x.shape) < 1:
+        raise ValueError("ops.batchnorm2d: every dimension must be >= 1")
+    B, C, H, W = x.shape
+    if x.numel() > _BN_MAX_ELEMS:
+        raise ValueError(f"ops.batchnorm2d: {x.numel()} elements do not fit "
+                         f"the kernel's 32-bit index")
+    named = [("weight", weight), ("bias", bias)]
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("ops.batchnorm2d: running_mean and running_var "
+                         "must both be given or both be None")
+    if running_mean is not None:
+        named += [("running_mean", running_mean),
+                  ("running_var", running_var)]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"ops.batchnorm2d: {name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"ops.batchnorm2d: {name} must be fp32, got "
+                            f"{t.dtype}")
+        if t.shape != (C,):
+            raise ValueError(f"ops.batchnorm2d: {name} must have shape "
+                             f"[{C}], got {tuple(t.shape)}")
+        if t.device != x.device:
+            raise ValueError(f"ops.batchnorm2d: {name} is on {t.device}, x "
+                             f"on {x.device}")
+    if running_mean is not None and not (running_mean.is_contiguous()
+                                         and running_var.is_contiguous()):
+        raise ValueError("ops.batchnorm2d: the running buffers are updated "
+                         "in place and must be contiguous")
+    if residual is not None:
+        if residual.dtype != x.dtype:
+            raise TypeError(f"ops.batchnorm2d: residual must have x's dtype "
+                            f"{x.dtype}, got {residual.dtype}")
+        if residual.shape != x.shape:
+            raise ValueError(f"ops.batchnorm2d: residual must have x's "
+                             f"shape {tuple(x.shape)}, got "
+                             f"{tuple(residual.shape)}")
+        if residual.device != x.device:
+            raise ValueError("ops.batchnorm2d: residual is on another "
+                             "device than x")
+        residual = residual.contiguous()
+    if momentum is None:
+        raise ValueError("ops.batchnorm2d: momentum=None (cumulative moving "
+                         "average) is not supported; pass a float in [0, 1]")
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) \
+            or not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"ops.batchnorm2d: momentum must be a float in "
+                         f"[0, 1], got {momentum!r}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) \
+            or not eps >= 0.0:
+        raise ValueError(f"ops.batchnorm2d: eps must be a float >= 0, got "
+                         f"{eps!r}")
+    if training and B * H * W == 1:
+        raise ValueError(f"ops.batchnorm2d: training needs more than one "
+                         f"value per channel, got input size "
+                         f"{tuple(x.shape)}")
+    if not training and running_mean is None:
+        raise ValueError("ops.batchnorm2d: training=False needs "
+                         "running_mean and running_var")
+    return _BatchNorm2d.apply(
+        x.contiguous(), weight.contiguous(), bias.contiguous(), residual,
+        running_mean, running_var, bool(training), float(momentum),
+        float(eps), bool(fuse_relu))
 
 
 # ---------------------------------------------------------------------------
