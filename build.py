@@ -48,7 +48,7 @@ def build(force: bool = False):
     targets = [
         # (output, sources, headers, extra flags)
         ("_rcclx.so", src("rcclx.cpp"), [], ["-L/opt/rocm/lib", "-lrccl"]),
-        ("_kernels.so", src("kernels.hip", "net_fused.hip",
+        ("_kernels.so", src("kernels.hip", "pointwise.hip", "net_fused.hip",
                             "linear_bf16.hip", "conv_bf16.hip",
                             "batchnorm.hip"),
          src("common.h", "gemm_bf16.h"), []),

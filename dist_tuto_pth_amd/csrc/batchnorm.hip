@@ -49,26 +49,8 @@
 
 namespace {
 
-using bf16_t = uint16_t;  // raw bits; all arithmetic goes through fp32
-
-constexpr int NT = 256;     // threads per block
-constexpr int GROUP = 8;    // elements per accumulation group
-constexpr int NWAVE = NT / 64;
-
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(bf16_t v) {
-  return __uint_as_float((uint32_t)v << 16);
-}
-
-// fp32 -> bf16, round-to-nearest-even, NaN kept quiet (torch's rule)
-__device__ __forceinline__ bf16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)0x7fc0;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-__device__ __forceinline__ void from_f(float v, float& o) { o = v; }
-__device__ __forceinline__ void from_f(float v, bf16_t& o) { o = f2bf(v); }
+constexpr int GROUP = 8;  // elements per accumulation group
+constexpr int NWAVE = BLK / 64;
 
 // one access of BYTES bytes
 template <int BYTES> struct Raw;
@@ -135,7 +117,7 @@ __device__ __forceinline__ Slice slice_of(int B, int C, int HW, int P) {
 // forward statistics
 // ---------------------------------------------------------------------------
 template <typename T, int V>
-__global__ __launch_bounds__(NT) void bn_stats_kernel(
+__global__ __launch_bounds__(BLK) void bn_stats_kernel(
     const T* __restrict__ x, float* __restrict__ ws, int B, int C, int HW,
     int P) {
   __shared__ float sh[NWAVE];
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(NT) void bn_stats_kernel(
   float acc[GROUP];
 #pragma unroll
   for (int j = 0; j < GROUP; ++j) acc[j] = 0.f;
-  for (uint32_t g = threadIdx.x; g * NA < nvec; g += NT) {
+  for (uint32_t g = threadIdx.x; g * NA < nvec; g += BLK) {
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
       const uint32_t q = g * NA + k;
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(NT) void bn_stats_kernel(
   // second pass over the slice (L2-resident): centred second moment
 #pragma unroll
   for (int j = 0; j < GROUP; ++j) acc[j] = 0.f;
-  for (uint32_t g = threadIdx.x; g * NA < nvec; g += NT) {
+  for (uint32_t g = threadIdx.x; g * NA < nvec; g += BLK) {
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
       const uint32_t q = g * NA + k;
@@ -233,13 +215,13 @@ __device__ __forceinline__ void channel_stats(const float* mean,
 // forward apply (+ residual, + ReLU)
 // ---------------------------------------------------------------------------
 template <typename T, int V>
-__global__ __launch_bounds__(NT) void bn_apply_kernel(
+__global__ __launch_bounds__(BLK) void bn_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ stat,
     const float* __restrict__ gamma, const float* __restrict__ beta,
     float eps, int eval, int relu, uint32_t nvec, uint32_t hwv, uint32_t C) {
-  for (uint32_t q = blockIdx.x * NT + threadIdx.x; q < nvec;
-       q += gridDim.x * NT) {
+  for (uint32_t q = blockIdx.x * BLK + threadIdx.x; q < nvec;
+       q += gridDim.x * BLK) {
     const uint32_t c = (q / hwv) % C;
     float mu, inv;
     channel_stats(mean, stat, eps, eval, c, mu, inv);
@@ -262,7 +244,7 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(
 // backward
 // ---------------------------------------------------------------------------
 template <typename T, int V>
-__global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(
+__global__ __launch_bounds__(BLK) void bn_bwd_reduce_kernel(
     const T* __restrict__ x, const T* __restrict__ gy,
     const T* __restrict__ y, const float* __restrict__ mean,
     const float* __restrict__ stat, float eps, int eval,
@@ -278,7 +260,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(
   float db[GROUP], dg[GROUP];
 #pragma unroll
   for (int j = 0; j < GROUP; ++j) db[j] = dg[j] = 0.f;
-  for (uint32_t g = threadIdx.x; g * NA < nvec; g += NT) {
+  for (uint32_t g = threadIdx.x; g * NA < nvec; g += BLK) {
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
       const uint32_t q = g * NA + k;
@@ -324,15 +306,15 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ ws, int C,
 }
 
 template <typename T, int V>
-__global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(
+__global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ gy,
     const T* __restrict__ y, const float* __restrict__ mean,
     const float* __restrict__ stat, const float* __restrict__ gamma,
     const float* __restrict__ dgamma, const float* __restrict__ dbeta,
     T* __restrict__ gx, T* __restrict__ gres, float eps, int eval, float n,
     uint32_t nvec, uint32_t hwv, uint32_t C) {
-  for (uint32_t q = blockIdx.x * NT + threadIdx.x; q < nvec;
-       q += gridDim.x * NT) {
+  for (uint32_t q = blockIdx.x * BLK + threadIdx.x; q < nvec;
+       q += gridDim.x * BLK) {
     const uint32_t c = (q / hwv) % C;
     const int64_t at = (int64_t)q * V;
     float fg[V], fy[V];
@@ -413,7 +395,7 @@ struct FwdArgs {
 
 template <typename T, int V>
 void launch_stats(const FwdArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((bn_stats_kernel<T, V>), dim3(a.C, a.S), dim3(NT), 0, st,
+  hipLaunchKernelGGL((bn_stats_kernel<T, V>), dim3(a.C, a.S), dim3(BLK), 0, st,
                      (const T*)a.x, (float*)a.ws, a.B, a.C, a.HW, a.P);
 }
 
@@ -421,8 +403,8 @@ template <typename T, int V>
 void launch_apply(const FwdArgs& a, hipStream_t st) {
   const uint32_t hwv = a.HW / V;
   const uint32_t nvec = (uint32_t)a.B * a.C * hwv;
-  hipLaunchKernelGGL((bn_apply_kernel<T, V>), dim3(grid_for(nvec, NT)),
-                     dim3(NT), 0, st, (const T*)a.x, (const T*)a.res, (T*)a.y,
+  hipLaunchKernelGGL((bn_apply_kernel<T, V>), dim3(grid_for(nvec, BLK)),
+                     dim3(BLK), 0, st, (const T*)a.x, (const T*)a.res, (T*)a.y,
                      (const float*)a.mean, (const float*)a.stat,
                      (const float*)a.gamma, (const float*)a.beta, a.eps,
                      a.eval, a.relu, nvec, hwv, (uint32_t)a.C);
@@ -436,7 +418,7 @@ struct BwdArgs {
 
 template <typename T, int V>
 void launch_bwd_reduce(const BwdArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, V>), dim3(a.C, a.S), dim3(NT),
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, V>), dim3(a.C, a.S), dim3(BLK),
                      0, st, (const T*)a.x, (const T*)a.gy, (const T*)a.y,
                      (const float*)a.mean, (const float*)a.stat, a.eps,
                      a.eval, (float*)a.ws, a.B, a.C, a.HW, a.P);
@@ -446,8 +428,8 @@ template <typename T, int V>
 void launch_bwd_apply(const BwdArgs& a, hipStream_t st) {
   const uint32_t hwv = a.HW / V;
   const uint32_t nvec = (uint32_t)a.B * a.C * hwv;
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V>), dim3(grid_for(nvec, NT)),
-                     dim3(NT), 0, st, (const T*)a.x, (const T*)a.gy,
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V>), dim3(grid_for(nvec, BLK)),
+                     dim3(BLK), 0, st, (const T*)a.x, (const T*)a.gy,
                      (const T*)a.y, (const float*)a.mean,
                      (const float*)a.stat, (const float*)a.gamma,
                      (const float*)a.dgamma, (const float*)a.dbeta, (T*)a.gx,

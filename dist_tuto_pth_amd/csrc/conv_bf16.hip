@@ -1,6 +1,4 @@
-// K17 — bf16 convolution on the CDNA4 matrix cores (gfx950), plus the bf16
-// forms of the two elementwise ops Net runs between its convolutions
-// (fused 2x2 maxpool+ReLU, channel dropout).
+// K17 — bf16 convolution on the CDNA4 matrix cores (gfx950).
 //
 // Numeric contract (ops.conv2d_bf16) is linear_bf16's: every GEMM operand
 // is bf16, products accumulate in fp32 on v_mfma_f32_16x16x32_bf16, each
@@ -308,7 +306,7 @@ struct NchwOut {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           if (m + j < M) {
-            store_out(out + ((int64_t)b * N + n) * HW + pix, v[j]);
+            from_f(v[j], out[((int64_t)b * N + n) * HW + pix]);
             if (++pix == HW) { pix = 0; ++b; }
           }
         }
@@ -321,7 +319,7 @@ struct NchwOut {
 // kernels
 // ---------------------------------------------------------------------------
 template <typename OutT>
-__global__ __launch_bounds__(NT) void conv_bf16_fwd_kernel(
+__global__ __launch_bounds__(BLK) void conv_bf16_fwd_kernel(
     ConvSrc x, Operand w, int M, OutT* __restrict__ out,
     const float* __restrict__ bias) {
   const int N = w.rows;
@@ -332,7 +330,7 @@ __global__ __launch_bounds__(NT) void conv_bf16_fwd_kernel(
 }
 
 template <typename OutT>
-__global__ __launch_bounds__(NT) void conv_bf16_bwd_x_kernel(
+__global__ __launch_bounds__(BLK) void conv_bf16_bwd_x_kernel(
     ConvSrc gy, const bf16_t* __restrict__ w, int M, int C,
     OutT* __restrict__ gx) {
   gemm_bf16_block<true, false>(PixelRowsLoader<true>(gy, M),
@@ -343,100 +341,12 @@ __global__ __launch_bounds__(NT) void conv_bf16_bwd_x_kernel(
                                NchwOut<OutT>{gx, C, gy.Hm * gy.Wm, gy.dHWm});
 }
 
-__global__ __launch_bounds__(NT) void conv_bf16_bwd_w_kernel(
+__global__ __launch_bounds__(BLK) void conv_bf16_bwd_w_kernel(
     GyRowsLoader gy, ConvSrc x, int red, int kchunk, float* __restrict__ gw,
     float* __restrict__ colsum) {
   gemm_bf16_block<false, false>(gy, TapRowsLoader{x}, gy.K, x.ntap, red,
                                 kchunk, (const float*)nullptr, 0, colsum,
                                 RowMajorOut<float>{gw, gy.K, x.ntap});
-}
-
-// ---------------------------------------------------------------------------
-// bf16 maxpool2d(2)+ReLU: the fp32 kernel's index encoding (bits 0-1 the
-// window slot, bit 2 "ReLU clipped"); max and ReLU only select values, so
-// the result is the fp32 op's, bit for bit.  H and W are even (checked on
-// the host), so the backward writes every input element.
-// ---------------------------------------------------------------------------
-__global__ void maxpool2d_relu_bf16_fwd_kernel(const bf16_t* __restrict__ x,
-                                               bf16_t* __restrict__ out,
-                                               int* __restrict__ idx,
-                                               int64_t planes, int H, int W) {
-  const int OH = H / 2, OW = W / 2;
-  const int64_t n = planes * OH * OW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = i / (OH * OW);
-    const int oh = (int)((i / OW) % OH);
-    const int ow = (int)(i % OW);
-    const bf16_t* xp = x + p * H * W + (int64_t)(oh * 2) * W + ow * 2;
-    const uint32_t top = *reinterpret_cast<const uint32_t*>(xp);
-    const uint32_t bot = *reinterpret_cast<const uint32_t*>(xp + W);
-    const bf16_t b0 = (bf16_t)(top & 0xffffu), b1 = (bf16_t)(top >> 16);
-    const bf16_t b2 = (bf16_t)(bot & 0xffffu), b3 = (bf16_t)(bot >> 16);
-    int am = 0;
-    bf16_t mb = b0;
-    float m = bf2f(b0);
-    if (bf2f(b1) > m) { m = bf2f(b1); mb = b1; am = 1; }
-    if (bf2f(b2) > m) { m = bf2f(b2); mb = b2; am = 2; }
-    if (bf2f(b3) > m) { m = bf2f(b3); mb = b3; am = 3; }
-    out[i] = m > 0.f ? mb : (bf16_t)0;
-    idx[i] = m > 0.f ? am : (am | 4);
-  }
-}
-
-__global__ void maxpool2d_relu_bf16_bwd_kernel(const bf16_t* __restrict__ gy,
-                                               const int* __restrict__ idx,
-                                               bf16_t* __restrict__ gx,
-                                               int64_t planes, int H, int W) {
-  const int OH = H / 2, OW = W / 2;
-  const int64_t n = planes * OH * OW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = i / (OH * OW);
-    const int oh = (int)((i / OW) % OH);
-    const int ow = (int)(i % OW);
-    bf16_t* gp = gx + p * H * W + (int64_t)(oh * 2) * W + ow * 2;
-    const int v = idx[i];
-    const int am = v & 3;
-    const uint32_t g = (v & 4) ? 0u : (uint32_t)gy[i];
-    const uint32_t top = am == 0 ? g : (am == 1 ? g << 16 : 0u);
-    const uint32_t bot = am == 2 ? g : (am == 3 ? g << 16 : 0u);
-    *reinterpret_cast<uint32_t*>(gp) = top;
-    *reinterpret_cast<uint32_t*>(gp + W) = bot;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// bf16 channel dropout: the fp32 kernel's plane index, RNG (mix32) and seed
-// advance, so equal (seed, p) gives the same channel mask.
-// ---------------------------------------------------------------------------
-__global__ void dropout2d_bf16_fwd_kernel(
-    const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
-    uint8_t* __restrict__ mask, int64_t planes, int64_t hw, float p,
-    float scale, const unsigned long long* __restrict__ sp) {
-  const uint32_t thresh = (uint32_t)(p * 4294967296.0);
-  const uint64_t seed = sp[0];
-  const int64_t n = planes * hw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t pl = i / hw;
-    uint32_t r = mix32(seed, (uint64_t)pl) << 16 |
-                 (mix32(seed ^ 0xabcd, pl) & 0xffff);
-    uint8_t keep = r >= thresh;
-    if (i % hw == 0) mask[pl] = keep;
-    out[i] = keep ? f2bf(bf2f(x[i]) * scale) : (bf16_t)0;
-  }
-}
-
-__global__ void dropout2d_bf16_bwd_kernel(const bf16_t* __restrict__ gy,
-                                          const uint8_t* __restrict__ mask,
-                                          bf16_t* __restrict__ gx,
-                                          int64_t planes, int64_t hw,
-                                          float scale) {
-  const int64_t n = planes * hw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    gx[i] = mask[i / hw] ? f2bf(bf2f(gy[i]) * scale) : (bf16_t)0;
 }
 
 // ---------------------------------------------------------------------------
@@ -501,10 +411,10 @@ void conv2d_bf16_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
   const Operand b = operand(w, a.ntap, K);
   const dim3 grid(cdiv(M, BM), cdiv(K, BN), 1);
   if (out_f32)
-    hipLaunchKernelGGL((conv_bf16_fwd_kernel<float>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((conv_bf16_fwd_kernel<float>), grid, dim3(BLK), 0,
                        S(stream), a, b, M, (float*)out, (const float*)bias);
   else
-    hipLaunchKernelGGL((conv_bf16_fwd_kernel<bf16_t>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((conv_bf16_fwd_kernel<bf16_t>), grid, dim3(BLK), 0,
                        S(stream), a, b, M, (bf16_t*)out, (const float*)bias);
 }
 
@@ -517,10 +427,10 @@ void conv2d_bf16_bwd_x(uintptr_t gy, uintptr_t w, uintptr_t gx, int B, int C,
   const ConvSrc a = src_gy(gy, d);
   const dim3 grid(cdiv(M, BM), cdiv(C, BN), 1);
   if (out_f32)
-    hipLaunchKernelGGL((conv_bf16_bwd_x_kernel<float>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((conv_bf16_bwd_x_kernel<float>), grid, dim3(BLK), 0,
                        S(stream), a, (const bf16_t*)w, M, C, (float*)gx);
   else
-    hipLaunchKernelGGL((conv_bf16_bwd_x_kernel<bf16_t>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((conv_bf16_bwd_x_kernel<bf16_t>), grid, dim3(BLK), 0,
                        S(stream), a, (const bf16_t*)w, M, C, (bf16_t*)gx);
 }
 
@@ -555,60 +465,12 @@ void conv2d_bf16_bwd_w(uintptr_t gy, uintptr_t x, uintptr_t gw, uintptr_t gb,
     c = (float*)part;
     cs = gb ? c + (int64_t)splits * n_gw : nullptr;
   }
-  hipLaunchKernelGGL(conv_bf16_bwd_w_kernel, grid, dim3(NT), 0, S(stream), a,
+  hipLaunchKernelGGL(conv_bf16_bwd_w_kernel, grid, dim3(BLK), 0, S(stream), a,
                      b, red, kchunk, c, cs);
   if (splits > 1)
-    hipLaunchKernelGGL(gw_combine_kernel, dim3(ew_grid(n_gw)), dim3(NT), 0,
-                       S(stream), (const float*)c, (float*)gw, n_gw,
-                       (const float*)cs, (float*)gb, K, splits);
-}
-
-static void check_even(int H, int W) {
-  if (H < 2 || W < 2 || (H & 1) || (W & 1))
-    throw std::invalid_argument(
-        "maxpool2d_relu (bf16): H and W must be even and >= 2");
-}
-
-void maxpool2d_relu_bf16_fwd(uintptr_t x, uintptr_t out, uintptr_t idx, int B,
-                             int C, int H, int W, uintptr_t stream) {
-  check_even(H, W);
-  const int64_t planes = (int64_t)B * C;
-  const int64_t n = planes * (H / 2) * (W / 2);
-  if (n <= 0) return;
-  hipLaunchKernelGGL(maxpool2d_relu_bf16_fwd_kernel, dim3(ew_grid(n)),
-                     dim3(NT), 0, S(stream), (const bf16_t*)x, (bf16_t*)out,
-                     (int*)idx, planes, H, W);
-}
-
-void maxpool2d_relu_bf16_bwd(uintptr_t gy, uintptr_t idx, uintptr_t gx, int B,
-                             int C, int H, int W, uintptr_t stream) {
-  check_even(H, W);
-  const int64_t planes = (int64_t)B * C;
-  const int64_t n = planes * (H / 2) * (W / 2);
-  if (n <= 0) return;
-  hipLaunchKernelGGL(maxpool2d_relu_bf16_bwd_kernel, dim3(ew_grid(n)),
-                     dim3(NT), 0, S(stream), (const bf16_t*)gy,
-                     (const int*)idx, (bf16_t*)gx, planes, H, W);
-}
-
-void dropout2d_bf16_fwd(uintptr_t x, uintptr_t out, uintptr_t mask,
-                        int64_t planes, int64_t hw, double p,
-                        uintptr_t seed_dev, uintptr_t stream) {
-  const float scale = 1.f / (1.f - (float)p);
-  launch_bump_seed(seed_dev, S(stream));
-  hipLaunchKernelGGL(dropout2d_bf16_fwd_kernel, dim3(ew_grid(planes * hw)),
-                     dim3(NT), 0, S(stream), (const bf16_t*)x, (bf16_t*)out,
-                     (uint8_t*)mask, planes, hw, (float)p, scale,
-                     (const unsigned long long*)seed_dev);
-}
-
-void dropout2d_bf16_bwd(uintptr_t gy, uintptr_t mask, uintptr_t gx,
-                        int64_t planes, int64_t hw, double scale,
-                        uintptr_t stream) {
-  hipLaunchKernelGGL(dropout2d_bf16_bwd_kernel, dim3(ew_grid(planes * hw)),
-                     dim3(NT), 0, S(stream), (const bf16_t*)gy,
-                     (const uint8_t*)mask, (bf16_t*)gx, planes, hw,
-                     (float)scale);
+    hipLaunchKernelGGL(gw_combine_kernel, dim3(grid_for(n_gw, BLK)),
+                       dim3(BLK), 0, S(stream), (const float*)c, (float*)gw,
+                       n_gw, (const float*)cs, (float*)gb, K, splits);
 }
 
 }  // namespace
@@ -618,8 +480,4 @@ void register_conv_bf16(pybind11::module_& m) {
   m.def("conv2d_bf16_bwd_x", &conv2d_bf16_bwd_x);
   m.def("conv2d_bf16_gw_splits", &conv2d_bf16_gw_splits);
   m.def("conv2d_bf16_bwd_w", &conv2d_bf16_bwd_w);
-  m.def("maxpool2d_relu_bf16_fwd", &maxpool2d_relu_bf16_fwd);
-  m.def("maxpool2d_relu_bf16_bwd", &maxpool2d_relu_bf16_bwd);
-  m.def("dropout2d_bf16_fwd", &dropout2d_bf16_fwd);
-  m.def("dropout2d_bf16_bwd", &dropout2d_bf16_bwd);
 }

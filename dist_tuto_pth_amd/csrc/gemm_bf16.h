@@ -20,11 +20,10 @@
 
 namespace {
 
-using bf16_t = uint16_t;  // raw bits; all arithmetic goes through fp32
 typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
 typedef __attribute__((ext_vector_type(4))) float frag_cd;
 
-constexpr int NT = 256;        // threads per block (4 waves, 2x2)
+static_assert(BLK == 256, "the block is 2x2 waves");
 constexpr int BM = 64;         // block tile rows
 constexpr int BN = 64;         // block tile cols
 constexpr int BK = 64;         // reduction depth per LDS tile
@@ -32,7 +31,7 @@ constexpr int LDS_LD = BK + 8; // 144-byte rows: 16-byte aligned; the
                                // 36-dword pitch puts 8 consecutive rows in
                                // 8 different 4-bank groups for the 16-byte
                                // fragment reads
-constexpr int NPASS = BM * BK / (NT * 8);  // 8-element chunks per thread
+constexpr int NPASS = BM * BK / (BLK * 8);  // 8-element chunks per thread
 static_assert(BK == 64, "lds_col swizzles the 8 chunks of a 64-deep row");
 
 // Column swizzle of the LDS tiles.  A transposed write sends the 8 lanes
@@ -43,21 +42,6 @@ static_assert(BK == 64, "lds_col swizzles the 8 chunks of a 64-deep row");
 __device__ __forceinline__ int lds_col(int row, int col) {
   return col ^ (((row >> 3) & 7) << 3);
 }
-
-__device__ __forceinline__ float bf2f(bf16_t v) {
-  return __uint_as_float((uint32_t)v << 16);
-}
-
-// fp32 -> bf16, round-to-nearest-even, NaN kept quiet (torch's rule)
-__device__ __forceinline__ bf16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)0x7fc0;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-
-__device__ __forceinline__ void store_out(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store_out(bf16_t* p, float v) { *p = f2bf(v); }
 
 union Chunk {  // 8 bf16
   uint4 v;
@@ -76,7 +60,7 @@ __device__ __forceinline__ Chunk zero_chunk() {
 // and k on `lo` (chunk runs along k); a transposed one puts k on `hi` and
 // rows on `lo` (chunk runs along the rows).
 __device__ __forceinline__ int chunk_hi(int p, int tid) {
-  return p * (NT / 8) + (tid >> 3);
+  return p * (BLK / 8) + (tid >> 3);
 }
 __device__ __forceinline__ int chunk_lo(int tid) { return (tid & 7) * 8; }
 
@@ -131,7 +115,7 @@ __device__ __forceinline__ Chunk load8(const Operand& o, int64_t idx,
         m.v = *reinterpret_cast<const uint4*>((const bf16_t*)o.mask + idx);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (!(bf2f(m.e[j]) > 0.f)) c.e[j] = 0;
+          if (!(to_f(m.e[j]) > 0.f)) c.e[j] = 0;
       }
     }
     return c;
@@ -142,7 +126,7 @@ __device__ __forceinline__ Chunk load8(const Operand& o, int64_t idx,
       bf16_t v = o.p[idx + j];
       if (o.mask) {
         const float m = o.mask_f32 ? ((const float*)o.mask)[idx + j]
-                                   : bf2f(((const bf16_t*)o.mask)[idx + j]);
+                                   : to_f(((const bf16_t*)o.mask)[idx + j]);
         if (!(m > 0.f)) v = 0;
       }
       c.e[j] = v;
@@ -158,7 +142,7 @@ __device__ __forceinline__ void gload(const Operand& o, int r0, int k0,
                                       int kend, int tid, Chunk (&reg)[NPASS]) {
 #pragma unroll
   for (int p = 0; p < NPASS; ++p) {
-    const int hi = p * (NT / 8) + (tid >> 3);  // 0..63
+    const int hi = p * (BLK / 8) + (tid >> 3);  // 0..63
     const int lo = (tid & 7) * 8;              // 0,8,..,56
     if (!TRANS) {
       const int r = r0 + hi, k = k0 + lo;      // chunk runs along k
@@ -199,7 +183,7 @@ struct RowMajorOut {
   int M, N;
   __device__ __forceinline__ void operator()(int z, int m, int n,
                                              float v) const {
-    store_out(C + ((int64_t)z * M + m) * N + n, v);
+    from_f(v, C[((int64_t)z * M + m) * N + n]);
   }
 };
 
@@ -272,7 +256,7 @@ __device__ __forceinline__ void gemm_bf16_block(
     if (do_colsum) {  // 4 threads per row, 2 chunks each, fixed order
       const bf16_t* row = &As[tid >> 2][(tid & 3) * 16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) csum += bf2f(row[j]);
+      for (int j = 0; j < 16; ++j) csum += to_f(row[j]);
     }
     __syncthreads();
   }
@@ -343,13 +327,6 @@ __global__ void gw_combine_kernel(const float* __restrict__ part,
       for (int z = 0; z < splits; ++z) s += gb_part[(int64_t)z * n_gb + i];
       gb[i] = s;
     }
-}
-
-inline int ew_grid(int64_t work) {
-  int64_t g = (work + NT - 1) / NT;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -1,6 +1,8 @@
-// kernels.hip — hand-written CDNA4 (gfx950/MI355X) kernels for every op
-// on the reference training path plus the
+// kernels.hip — hand-written CDNA4 (gfx950/MI355X) kernels for the fp32
+// ops of the reference training path (K1/K2 conv, K7/K8
+// linear, K9/K10 log_softmax and NLL, K11-K13 SGD) plus the
 // local-reduction primitives of the hand-rolled ring all-reduce (K14).
+// The pointwise and pooling ops (K3-K6) live in pointwise.hip.
 //
 // The reference gets these ops implicitly from torch
 // (Net.forward train_dist.py:64-71, SGD train_dist.py:110,124); here
@@ -13,11 +15,12 @@
 // ring-allreduce reduction path (BASELINE config 5).
 // Build: hipcc --offload-arch=gfx950 (build.py).  No CUDA paths.
 //
-// This file also owns PYBIND11_MODULE; the fused whole-Net step
-// (net_fused.hip), the bf16 linear (linear_bf16.hip), the bf16
-// convolution (conv_bf16.hip) and batch normalization (batchnorm.hip)
-// register their bindings through register_net_fused() /
-// register_linear_bf16() / register_conv_bf16() / register_batchnorm().
+// This file also owns PYBIND11_MODULE; the pointwise ops (pointwise.hip),
+// the fused whole-Net step (net_fused.hip), the bf16 linear
+// (linear_bf16.hip), the bf16 convolution (conv_bf16.hip) and batch
+// normalization (batchnorm.hip) register their bindings through
+// register_pointwise() / register_net_fused() / register_linear_bf16() /
+// register_conv_bf16() / register_batchnorm().
 
 #include "common.h"
 
@@ -182,157 +185,6 @@ __global__ void conv2d_bwd_w_kernel(const float* __restrict__ x,
       else atomicAdd(&gb[k], acc);
     }
   }
-}
-
-// ===========================================================================
-// K3+K4 — fused 2x2/stride-2 maxpool + ReLU (train_dist.py:65-66).
-// Forward stores the winning index (0..3) packed with the sign; the
-// backward writes all four window slots (pool windows are disjoint), so
-// gx needs no pre-zeroing pass.
-// ===========================================================================
-__global__ void maxpool2d_relu_fwd_kernel(const float* __restrict__ x,
-                                          float* __restrict__ out,
-                                          int* __restrict__ idx,
-                                          int64_t planes, int H, int W) {
-  const int OH = H / 2, OW = W / 2;
-  const int64_t n = planes * OH * OW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = i / (OH * OW);
-    const int oh = (int)((i / OW) % OH);
-    const int ow = (int)(i % OW);
-    const float* xp = x + p * H * W + (oh * 2) * W + ow * 2;
-    float v0 = xp[0], v1 = xp[1], v2 = xp[W], v3 = xp[W + 1];
-    int am = 0;
-    float m = v0;
-    if (v1 > m) { m = v1; am = 1; }
-    if (v2 > m) { m = v2; am = 2; }
-    if (v3 > m) { m = v3; am = 3; }
-    out[i] = m > 0.f ? m : 0.f;
-    idx[i] = m > 0.f ? am : (am | 4);  // bit2: ReLU clipped
-  }
-}
-
-__global__ void maxpool2d_relu_bwd_kernel(const float* __restrict__ gy,
-                                          const int* __restrict__ idx,
-                                          float* __restrict__ gx,
-                                          int64_t planes, int H, int W) {
-  const int OH = H / 2, OW = W / 2;
-  const int64_t n = planes * OH * OW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = i / (OH * OW);
-    const int oh = (int)((i / OW) % OH);
-    const int ow = (int)(i % OW);
-    float* gp = gx + p * H * W + (oh * 2) * W + ow * 2;
-    const int v = idx[i];
-    const int am = v & 3;
-    const float g = (v & 4) ? 0.f : gy[i];
-    gp[0] = am == 0 ? g : 0.f;
-    gp[1] = am == 1 ? g : 0.f;
-    gp[W] = am == 2 ? g : 0.f;
-    gp[W + 1] = am == 3 ? g : 0.f;
-  }
-}
-
-// ===========================================================================
-// K4 — standalone ReLU (elementwise, float4-vectorized)
-// ===========================================================================
-__global__ void relu_fwd_kernel(const float* __restrict__ x,
-                                float* __restrict__ out, int64_t n) {
-  const int64_t n4 = n / 4;
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  float4* o4 = reinterpret_cast<float4*>(out);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 v = x4[i];
-    v.x = v.x > 0.f ? v.x : 0.f;
-    v.y = v.y > 0.f ? v.y : 0.f;
-    v.z = v.z > 0.f ? v.z : 0.f;
-    v.w = v.w > 0.f ? v.w : 0.f;
-    o4[i] = v;
-  }
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = x[i] > 0.f ? x[i] : 0.f;
-}
-
-__global__ void relu_bwd_kernel(const float* __restrict__ gy,
-                                const float* __restrict__ out,
-                                float* __restrict__ gx, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    gx[i] = out[i] > 0.f ? gy[i] : 0.f;
-}
-
-// ===========================================================================
-// K5/K6 — dropout.  Counter-based hash RNG (wang/xxhash-style mix of
-// (seed, index), mix32 in common.h): stateless, reproducible from the
-// device seed, no RNG-state tensor.  Channelwise variant draws one
-// number per (batch, channel) plane (Dropout2d, train_dist.py:60).
-// ===========================================================================
-// device-side seed bump: lets dropout RNG advance across hipGraph
-// replays (the seed lives in device memory; one tiny kernel increments
-// it before each dropout draw, stream-ordered).
-__global__ void bump_seed_kernel(unsigned long long* s) {
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    *s += SEED_INC;
-}
-
-__global__ void dropout_fwd_kernel(const float* __restrict__ x,
-                                   float* __restrict__ out,
-                                   uint8_t* __restrict__ mask, int64_t n,
-                                   float p, float scale,
-                                   const unsigned long long* __restrict__ sp) {
-  const uint32_t thresh = (uint32_t)(p * 4294967296.0);
-  const uint64_t seed = sp[0];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t r = mix32(seed, (uint64_t)i) << 16 | (mix32(seed ^ 0xabcd, i) & 0xffff);
-    uint8_t keep = r >= thresh;
-    mask[i] = keep;
-    out[i] = keep ? x[i] * scale : 0.f;
-  }
-}
-
-__global__ void dropout_bwd_kernel(const float* __restrict__ gy,
-                                   const uint8_t* __restrict__ mask,
-                                   float* __restrict__ gx, int64_t n,
-                                   float scale) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    gx[i] = mask[i] ? gy[i] * scale : 0.f;
-}
-
-__global__ void dropout2d_fwd_kernel(const float* __restrict__ x,
-                                     float* __restrict__ out,
-                                     uint8_t* __restrict__ mask,
-                                     int64_t planes, int64_t hw, float p,
-                                     float scale,
-                                     const unsigned long long* __restrict__ sp) {
-  const uint32_t thresh = (uint32_t)(p * 4294967296.0);
-  const uint64_t seed = sp[0];
-  const int64_t n = planes * hw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t pl = i / hw;
-    uint32_t r = mix32(seed, (uint64_t)pl) << 16 |
-                 (mix32(seed ^ 0xabcd, pl) & 0xffff);
-    uint8_t keep = r >= thresh;
-    if (i % hw == 0) mask[pl] = keep;
-    out[i] = keep ? x[i] * scale : 0.f;
-  }
-}
-
-__global__ void dropout2d_bwd_kernel(const float* __restrict__ gy,
-                                     const uint8_t* __restrict__ mask,
-                                     float* __restrict__ gx,
-                                     int64_t planes, int64_t hw,
-                                     float scale) {
-  const int64_t n = planes * hw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    gx[i] = mask[i / hw] ? gy[i] * scale : 0.f;
 }
 
 // ===========================================================================
@@ -818,74 +670,6 @@ void conv2d_bwd(uintptr_t x, uintptr_t w, uintptr_t gy, uintptr_t gx,
   }
 }
 
-void maxpool2d_relu_fwd(uintptr_t x, uintptr_t out, uintptr_t idx, int B,
-                        int C, int H, int W, uintptr_t stream) {
-  const int64_t planes = (int64_t)B * C;
-  const int64_t n = planes * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(maxpool2d_relu_fwd_kernel, dim3(grid_for(n, BLK)),
-                     dim3(BLK), 0, S(stream), (const float*)x, (float*)out,
-                     (int*)idx, planes, H, W);
-}
-
-void maxpool2d_relu_bwd(uintptr_t gy, uintptr_t idx, uintptr_t gx, int B,
-                        int C, int H, int W, uintptr_t stream) {
-  const int64_t planes = (int64_t)B * C;
-  const int64_t n = planes * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(maxpool2d_relu_bwd_kernel, dim3(grid_for(n, BLK)),
-                     dim3(BLK), 0, S(stream), (const float*)gy,
-                     (const int*)idx, (float*)gx, planes, H, W);
-}
-
-void relu_fwd(uintptr_t x, uintptr_t out, int64_t n, uintptr_t stream) {
-  hipLaunchKernelGGL(relu_fwd_kernel, dim3(grid_for(n, BLK, 4)), dim3(BLK),
-                     0, S(stream), (const float*)x, (float*)out, n);
-}
-
-void relu_bwd(uintptr_t gy, uintptr_t out, uintptr_t gx, int64_t n,
-              uintptr_t stream) {
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n, BLK)), dim3(BLK), 0,
-                     S(stream), (const float*)gy, (const float*)out,
-                     (float*)gx, n);
-}
-
-void dropout_fwd(uintptr_t x, uintptr_t out, uintptr_t mask, int64_t n,
-                 double p, uintptr_t seed_dev, uintptr_t stream) {
-  const float scale = 1.f / (1.f - (float)p);
-  launch_bump_seed(seed_dev, S(stream));
-  hipLaunchKernelGGL(dropout_fwd_kernel, dim3(grid_for(n, BLK)), dim3(BLK),
-                     0, S(stream), (const float*)x, (float*)out,
-                     (uint8_t*)mask, n, (float)p, scale,
-                     (const unsigned long long*)seed_dev);
-}
-
-void dropout_bwd(uintptr_t gy, uintptr_t mask, uintptr_t gx, int64_t n,
-                 double scale, uintptr_t stream) {
-  hipLaunchKernelGGL(dropout_bwd_kernel, dim3(grid_for(n, BLK)), dim3(BLK),
-                     0, S(stream), (const float*)gy, (const uint8_t*)mask,
-                     (float*)gx, n, (float)scale);
-}
-
-void dropout2d_fwd(uintptr_t x, uintptr_t out, uintptr_t mask,
-                   int64_t planes, int64_t hw, double p,
-                   uintptr_t seed_dev, uintptr_t stream) {
-  const float scale = 1.f / (1.f - (float)p);
-  launch_bump_seed(seed_dev, S(stream));
-  hipLaunchKernelGGL(dropout2d_fwd_kernel,
-                     dim3(grid_for(planes * hw, BLK)), dim3(BLK), 0,
-                     S(stream), (const float*)x, (float*)out,
-                     (uint8_t*)mask, planes, hw, (float)p, scale,
-                     (const unsigned long long*)seed_dev);
-}
-
-void dropout2d_bwd(uintptr_t gy, uintptr_t mask, uintptr_t gx,
-                   int64_t planes, int64_t hw, double scale,
-                   uintptr_t stream) {
-  hipLaunchKernelGGL(dropout2d_bwd_kernel,
-                     dim3(grid_for(planes * hw, BLK)), dim3(BLK), 0,
-                     S(stream), (const float*)gy, (const uint8_t*)mask,
-                     (float*)gx, planes, hw, (float)scale);
-}
-
 void linear_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
                 int B, int K, int N, bool fuse_relu, uintptr_t stream) {
   const int64_t need = (int64_t)N * K * sizeof(float);
@@ -1049,15 +833,12 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 
 }  // namespace
 
-void launch_bump_seed(uintptr_t seed_ptr, hipStream_t stream) {
-  hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(64), 0, stream,
-                     (unsigned long long*)seed_ptr);
-}
-
-// the fused whole-Net step lives in net_fused.hip, K16 (bf16 MFMA
-// linear, bf16 dropout) in linear_bf16.hip, K17 (bf16 MFMA convolution,
-// bf16 maxpool+ReLU and channel dropout) in conv_bf16.hip, K18 (batch
-// normalization with fused add and ReLU) in batchnorm.hip
+// K3-K6 (pool, ReLU, dropout and the bf16 cast, both dtypes) live in
+// pointwise.hip, the fused whole-Net step in net_fused.hip, K16 (bf16 MFMA
+// linear) in linear_bf16.hip, K17 (bf16 MFMA convolution) in
+// conv_bf16.hip, K18 (batch normalization with fused add and ReLU) in
+// batchnorm.hip
+void register_pointwise(pybind11::module_& m);
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
@@ -1067,14 +848,6 @@ PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_bwd", &conv2d_bwd);
-  m.def("maxpool2d_relu_fwd", &maxpool2d_relu_fwd);
-  m.def("maxpool2d_relu_bwd", &maxpool2d_relu_bwd);
-  m.def("relu_fwd", &relu_fwd);
-  m.def("relu_bwd", &relu_bwd);
-  m.def("dropout_fwd", &dropout_fwd);
-  m.def("dropout_bwd", &dropout_bwd);
-  m.def("dropout2d_fwd", &dropout2d_fwd);
-  m.def("dropout2d_bwd", &dropout2d_bwd);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
   m.def("log_softmax_fwd", &log_softmax_fwd);
@@ -1088,6 +861,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("copy_throttled", &copy_throttled);
   m.def("reduce_columns", &reduce_columns);
   m.def("scale_f32", &scale_f32);
+  register_pointwise(m);
   register_net_fused(m);
   register_linear_bf16(m);
   register_conv_bf16(m);

@@ -4,7 +4,7 @@
 // accumulate in fp32 on v_mfma_f32_16x16x32_bf16, and each result is rounded
 // ONCE (RNE) from the fp32 accumulator to its output dtype.  fp32 operands
 // (master weights, the first layer's input, an fp32 upstream gradient) are
-// rounded to bf16 by cast_f32_to_bf16 first.
+// rounded to bf16 by cast_f32_to_bf16 (pointwise.hip) first.
 //
 // One GEMM (gemm_bf16.h, shared with the bf16 convolution in
 // conv_bf16.hip) serves all three products.  It computes
@@ -30,32 +30,11 @@
 namespace {
 
 // ---------------------------------------------------------------------------
-// cast fp32 -> bf16
-// ---------------------------------------------------------------------------
-__global__ void cast_f32_to_bf16_kernel(const float* __restrict__ src,
-                                        bf16_t* __restrict__ dst, int64_t n,
-                                        int64_t nvec) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t nth = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = tid; i < nvec; i += nth) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i];
-    const float4 b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    Chunk c;
-    c.e[0] = f2bf(a.x); c.e[1] = f2bf(a.y);
-    c.e[2] = f2bf(a.z); c.e[3] = f2bf(a.w);
-    c.e[4] = f2bf(b.x); c.e[5] = f2bf(b.y);
-    c.e[6] = f2bf(b.z); c.e[7] = f2bf(b.w);
-    reinterpret_cast<uint4*>(dst)[i] = c.v;
-  }
-  for (int64_t i = nvec * 8 + tid; i < n; i += nth) dst[i] = f2bf(src[i]);
-}
-
-// ---------------------------------------------------------------------------
 // the GEMM kernel: gemm_bf16_block (gemm_bf16.h) behind the plain loaders,
 // row-major output.  grid = (m tiles, n tiles, splits).
 // ---------------------------------------------------------------------------
 template <bool TA, bool TB, typename OutT>
-__global__ __launch_bounds__(NT) void gemm_bf16_kernel(
+__global__ __launch_bounds__(BLK) void gemm_bf16_kernel(
     Operand A, Operand B, int Kred, int kchunk, OutT* __restrict__ C,
     const float* __restrict__ bias, int relu, float* __restrict__ colsum) {
   const int M = A.rows, N = B.rows;
@@ -65,50 +44,11 @@ __global__ __launch_bounds__(NT) void gemm_bf16_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// bf16 elementwise dropout: the RNG (mix32) and the seed advance
-// (launch_bump_seed) ARE the fp32 kernels' (common.h), and the element index
-// and seed pointer are the same, so equal (seed, p) gives equal masks.
-// ---------------------------------------------------------------------------
-__global__ void dropout_bf16_fwd_kernel(
-    const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
-    uint8_t* __restrict__ mask, int64_t n, float p, float scale,
-    const unsigned long long* __restrict__ sp) {
-  const uint32_t thresh = (uint32_t)(p * 4294967296.0);
-  const uint64_t seed = sp[0];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t r = mix32(seed, (uint64_t)i) << 16 |
-                 (mix32(seed ^ 0xabcd, i) & 0xffff);
-    uint8_t keep = r >= thresh;
-    mask[i] = keep;
-    out[i] = keep ? f2bf(bf2f(x[i]) * scale) : (bf16_t)0;
-  }
-}
-
-__global__ void dropout_bf16_bwd_kernel(const bf16_t* __restrict__ gy,
-                                        const uint8_t* __restrict__ mask,
-                                        bf16_t* __restrict__ gx, int64_t n,
-                                        float scale) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    gx[i] = mask[i] ? f2bf(bf2f(gy[i]) * scale) : (bf16_t)0;
-}
-
-// ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
 static void check_dims(int B, int K, int N) {
   if (B < 1 || K < 1 || N < 1)
     throw std::invalid_argument("linear_bf16: B, K, N must be >= 1");
-}
-
-void cast_f32_to_bf16(uintptr_t src, uintptr_t dst, int64_t n,
-                      uintptr_t stream) {
-  if (n <= 0) return;
-  const int64_t nvec = (src % 16 == 0 && dst % 16 == 0) ? n / 8 : 0;
-  hipLaunchKernelGGL(cast_f32_to_bf16_kernel, dim3(ew_grid((n + 7) / 8)),
-                     dim3(NT), 0, S(stream), (const float*)src, (bf16_t*)dst,
-                     n, nvec);
 }
 
 // out[B,N] = x[B,K] · w[N,K]ᵀ (+ bias) (ReLU); x, w bf16
@@ -120,11 +60,11 @@ void linear_bf16_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
   const dim3 grid(cdiv(B, BM), cdiv(N, BN), 1);
   if (out_f32)
     hipLaunchKernelGGL((gemm_bf16_kernel<false, false, float>), grid,
-                       dim3(NT), 0, S(stream), a, b, K, K, (float*)out,
+                       dim3(BLK), 0, S(stream), a, b, K, K, (float*)out,
                        (const float*)bias, (int)relu, (float*)nullptr);
   else
     hipLaunchKernelGGL((gemm_bf16_kernel<false, false, bf16_t>), grid,
-                       dim3(NT), 0, S(stream), a, b, K, K, (bf16_t*)out,
+                       dim3(BLK), 0, S(stream), a, b, K, K, (bf16_t*)out,
                        (const float*)bias, (int)relu, (float*)nullptr);
 }
 
@@ -138,12 +78,12 @@ void linear_bf16_bwd_x(uintptr_t gy, uintptr_t w, uintptr_t mask,
   const Operand b = operand(w, K, K);  // B(n=k_col, k=n) = w[n*K + k_col]
   const dim3 grid(cdiv(B, BM), cdiv(K, BN), 1);
   if (out_f32)
-    hipLaunchKernelGGL((gemm_bf16_kernel<false, true, float>), grid, dim3(NT),
+    hipLaunchKernelGGL((gemm_bf16_kernel<false, true, float>), grid, dim3(BLK),
                        0, S(stream), a, b, N, N, (float*)gx,
                        (const float*)nullptr, 0, (float*)nullptr);
   else
     hipLaunchKernelGGL((gemm_bf16_kernel<false, true, bf16_t>), grid,
-                       dim3(NT), 0, S(stream), a, b, N, N, (bf16_t*)gx,
+                       dim3(BLK), 0, S(stream), a, b, N, N, (bf16_t*)gx,
                        (const float*)nullptr, 0, (float*)nullptr);
 }
 
@@ -175,40 +115,20 @@ void linear_bf16_bwd_w(uintptr_t gy, uintptr_t x, uintptr_t mask,
     c = (float*)part;
     cs = gb ? c + (int64_t)splits * n_gw : nullptr;
   }
-  hipLaunchKernelGGL((gemm_bf16_kernel<true, true, float>), grid, dim3(NT), 0,
+  hipLaunchKernelGGL((gemm_bf16_kernel<true, true, float>), grid, dim3(BLK), 0,
                      S(stream), a, b, B, kchunk, c, (const float*)nullptr, 0,
                      cs);
   if (splits > 1)
-    hipLaunchKernelGGL(gw_combine_kernel, dim3(ew_grid(n_gw)), dim3(NT), 0,
-                       S(stream), (const float*)c, (float*)gw, n_gw,
-                       (const float*)cs, (float*)gb, N, splits);
-}
-
-void dropout_bf16_fwd(uintptr_t x, uintptr_t out, uintptr_t mask, int64_t n,
-                      double p, uintptr_t seed_dev, uintptr_t stream) {
-  const float scale = 1.f / (1.f - (float)p);
-  launch_bump_seed(seed_dev, S(stream));
-  hipLaunchKernelGGL(dropout_bf16_fwd_kernel, dim3(ew_grid(n)), dim3(NT), 0,
-                     S(stream), (const bf16_t*)x, (bf16_t*)out,
-                     (uint8_t*)mask, n, (float)p, scale,
-                     (const unsigned long long*)seed_dev);
-}
-
-void dropout_bf16_bwd(uintptr_t gy, uintptr_t mask, uintptr_t gx, int64_t n,
-                      double scale, uintptr_t stream) {
-  hipLaunchKernelGGL(dropout_bf16_bwd_kernel, dim3(ew_grid(n)), dim3(NT), 0,
-                     S(stream), (const bf16_t*)gy, (const uint8_t*)mask,
-                     (bf16_t*)gx, n, (float)scale);
+    hipLaunchKernelGGL(gw_combine_kernel, dim3(grid_for(n_gw, BLK)),
+                       dim3(BLK), 0, S(stream), (const float*)c, (float*)gw,
+                       n_gw, (const float*)cs, (float*)gb, N, splits);
 }
 
 }  // namespace
 
 void register_linear_bf16(pybind11::module_& m) {
-  m.def("cast_f32_to_bf16", &cast_f32_to_bf16);
   m.def("linear_bf16_fwd", &linear_bf16_fwd);
   m.def("linear_bf16_bwd_x", &linear_bf16_bwd_x);
   m.def("linear_bf16_gw_splits", &linear_bf16_gw_splits);
   m.def("linear_bf16_bwd_w", &linear_bf16_bwd_w);
-  m.def("dropout_bf16_fwd", &dropout_bf16_fwd);
-  m.def("dropout_bf16_bwd", &dropout_bf16_bwd);
 }

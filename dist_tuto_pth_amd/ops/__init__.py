@@ -2,15 +2,17 @@
 
 Every op the reference's ``Net.forward`` + SGD step trigger implicitly
 through torch (train_dist.py:58-71,110,118-124) is a hand-written CDNA4
-HIP kernel here (``csrc/kernels.hip``), with forward *and* backward:
+HIP kernel here, with forward *and* backward (``csrc/kernels.hip``; K3-K6
+in ``csrc/pointwise.hip``, K16-K18 in the files named at their sections):
 
   K1/K2  conv2d (direct, LDS-tiled)        -> conv2d
-  K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu
+  K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu (fp32, bf16)
+  K4     ReLU                              -> relu
   K5/K6  dropout2d (channel) / dropout     -> dropout2d / dropout
+                                              (fp32, bf16)
   K7/K8  linear (+fused ReLU epilogue)     -> linear
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
-         bf16 pool+ReLU / channel dropout   -> maxpool2d_relu / dropout2d
   K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
@@ -41,6 +43,20 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptr(t) -> int:
+    """Device address of an optional tensor; 0 for ``None``."""
+    return t.data_ptr() if t is not None else 0
+
+
+def _require_fp32(op, hint="", **tensors):
+    """The kernels behind ``op`` read and write fp32: refuse a CUDA tensor
+    of any other dtype before its pointer reaches them."""
+    for name, t in tensors.items():
+        if t is not None and t.dtype != torch.float32 and t.is_cuda:
+            raise TypeError(f"ops.{op} is fp32 only on GPU, got {name} of "
+                            f"dtype {t.dtype}{hint}")
+
+
 # ---------------------------------------------------------------------------
 # K1/K2 — direct convolution (no padding, stride 1: the only form Net uses)
 # ---------------------------------------------------------------------------
@@ -54,8 +70,7 @@ class _Conv2d(torch.autograd.Function):
             K, _, R, S = w.shape
             OH, OW = H - R + 1, W - S + 1
             out = torch.empty(B, K, OH, OW, device=x.device, dtype=x.dtype)
-            k.conv2d_fwd(x.data_ptr(), w.data_ptr(),
-                         b.data_ptr() if b is not None else 0,
+            k.conv2d_fwd(x.data_ptr(), w.data_ptr(), _ptr(b),
                          out.data_ptr(), B, C, H, W, K, R, S, _stream())
             return out
         return F.conv2d(x, w, b)
@@ -73,8 +88,7 @@ class _Conv2d(torch.autograd.Function):
             gb = torch.empty(K, device=x.device, dtype=x.dtype) \
                 if ctx.needs_input_grad[2] else None
             k.conv2d_bwd(x.data_ptr(), w.data_ptr(), gy.data_ptr(),
-                         gx.data_ptr(), gw.data_ptr(),
-                         gb.data_ptr() if gb is not None else 0,
+                         gx.data_ptr(), gw.data_ptr(), _ptr(gb),
                          B, C, H, W, K, R, S, _stream())
             return gx, gw, gb
         gx = torch.nn.grad.conv2d_input(x.shape, w, gy)
@@ -84,6 +98,7 @@ class _Conv2d(torch.autograd.Function):
 
 
 def conv2d(x, w, b=None):
+    _require_fp32("conv2d", x=x, w=w, b=b)
     return _Conv2d.apply(x.contiguous(), w, b)
 
 
@@ -102,10 +117,9 @@ class _MaxPool2dRelu(torch.autograd.Function):
             out = torch.empty(B, C, OH, OW, device=x.device, dtype=x.dtype)
             idx = torch.empty(B, C, OH, OW, device=x.device,
                               dtype=torch.int32)
-            fwd = k.maxpool2d_relu_bf16_fwd if x.dtype == torch.bfloat16 \
-                else k.maxpool2d_relu_fwd
-            fwd(_aligned4(x).data_ptr(), out.data_ptr(), idx.data_ptr(),
-                B, C, H, W, _stream())
+            k.maxpool2d_relu_fwd(
+                _aligned4(x).data_ptr(), out.data_ptr(), idx.data_ptr(),
+                B, C, H, W, x.dtype == torch.bfloat16, _stream())
             ctx.save_for_backward(idx)
             ctx.in_shape = x.shape
             return out
@@ -122,12 +136,13 @@ class _MaxPool2dRelu(torch.autograd.Function):
             (idx,) = ctx.saved_tensors
             k = _k()
             B, C, H, W = ctx.in_shape
-            gx = torch.empty(ctx.in_shape, device=gy.device,
-                             dtype=gy.dtype)  # kernel writes all slots
-            bwd = k.maxpool2d_relu_bf16_bwd if gy.dtype == torch.bfloat16 \
-                else k.maxpool2d_relu_bwd
-            bwd(gy.data_ptr(), idx.data_ptr(), gx.data_ptr(), B, C, H, W,
-                _stream())
+            # the kernel writes every slot of every window; an odd last
+            # row or column is in no window and gets no gradient
+            alloc = torch.zeros if H % 2 or W % 2 else torch.empty
+            gx = alloc(ctx.in_shape, device=gy.device, dtype=gy.dtype)
+            k.maxpool2d_relu_bwd(
+                gy.data_ptr(), idx.data_ptr(), gx.data_ptr(), B, C, H, W,
+                gy.dtype == torch.bfloat16, _stream())
             return gx
         idx, pooled = ctx.saved_tensors
         gy = gy * (pooled > 0)
@@ -159,6 +174,7 @@ def maxpool2d_relu(x):
 
 
 def relu(x):
+    _require_fp32("relu", x=x)
     return _Relu.apply(x.contiguous())
 
 
@@ -221,17 +237,16 @@ class _Dropout(torch.autograd.Function):
                 hw = x.numel() // (B * C)
                 mask = torch.empty(B * C, device=x.device,
                                    dtype=torch.uint8)
-                fwd = k.dropout2d_bf16_fwd if x.dtype == torch.bfloat16 \
-                    else k.dropout2d_fwd
-                fwd(x.data_ptr(), out.data_ptr(), mask.data_ptr(), B * C,
-                    hw, p, _seed_ptr(x.device), _stream())
+                k.dropout2d_fwd(x.data_ptr(), out.data_ptr(),
+                                mask.data_ptr(), B * C, hw, p,
+                                _seed_ptr(x.device),
+                                x.dtype == torch.bfloat16, _stream())
             else:
                 mask = torch.empty(x.numel(), device=x.device,
                                    dtype=torch.uint8)
-                fwd = k.dropout_bf16_fwd if x.dtype == torch.bfloat16 \
-                    else k.dropout_fwd
-                fwd(x.data_ptr(), out.data_ptr(), mask.data_ptr(),
-                    x.numel(), p, _seed_ptr(x.device), _stream())
+                k.dropout_fwd(x.data_ptr(), out.data_ptr(), mask.data_ptr(),
+                              x.numel(), p, _seed_ptr(x.device),
+                              x.dtype == torch.bfloat16, _stream())
             ctx.save_for_backward(mask)
             ctx.meta = (scale, channelwise, x.shape)
             ctx.mask = mask
@@ -262,15 +277,13 @@ class _Dropout(torch.autograd.Function):
             if channelwise:
                 B, C = shape[0], shape[1]
                 hw = gy.numel() // (B * C)
-                bwd = k.dropout2d_bf16_bwd if gy.dtype == torch.bfloat16 \
-                    else k.dropout2d_bwd
-                bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(), B * C,
-                    hw, scale, _stream())
+                k.dropout2d_bwd(gy.data_ptr(), mask.data_ptr(),
+                                gx.data_ptr(), B * C, hw, scale,
+                                gy.dtype == torch.bfloat16, _stream())
             else:
-                bwd = k.dropout_bf16_bwd if gy.dtype == torch.bfloat16 \
-                    else k.dropout_bwd
-                bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(),
-                    gy.numel(), scale, _stream())
+                k.dropout_bwd(gy.data_ptr(), mask.data_ptr(), gx.data_ptr(),
+                              gy.numel(), scale,
+                              gy.dtype == torch.bfloat16, _stream())
             return gx, None, None, None
         if channelwise:
             B, C = shape[0], shape[1]
@@ -314,8 +327,7 @@ class _Linear(torch.autograd.Function):
             B, K = x.shape
             N = w.shape[0]
             out = torch.empty(B, N, device=x.device, dtype=x.dtype)
-            k.linear_fwd(x.data_ptr(), w.data_ptr(),
-                         b.data_ptr() if b is not None else 0,
+            k.linear_fwd(x.data_ptr(), w.data_ptr(), _ptr(b),
                          out.data_ptr(), B, K, N, fuse_relu, _stream())
         else:
             out = F.linear(x, w, b)
@@ -340,8 +352,7 @@ class _Linear(torch.autograd.Function):
                 if ctx.has_bias else None
             k.linear_bwd(x.data_ptr(), w.data_ptr(), gy.data_ptr(),
                          out.data_ptr() if ctx.fuse_relu else 0,
-                         gx.data_ptr(), gw.data_ptr(),
-                         gb.data_ptr() if gb is not None else 0,
+                         gx.data_ptr(), gw.data_ptr(), _ptr(gb),
                          B, K, N, _stream())
             return gx, gw, gb, None
         if ctx.fuse_relu:
@@ -353,12 +364,8 @@ class _Linear(torch.autograd.Function):
 
 
 def linear(x, w, b=None, fuse_relu=False):
-    if x.is_cuda:
-        for name, t in (("x", x), ("w", w), ("b", b)):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError(
-                    f"ops.linear is fp32 only on GPU, got {name} of dtype "
-                    f"{t.dtype}; use ops.linear_bf16 for bf16 operands")
+    _require_fp32("linear", "; use ops.linear_bf16 for bf16 operands",
+                  x=x, w=w, b=b)
     return _Linear.apply(x.contiguous(), w, b, fuse_relu)
 
 
@@ -395,8 +402,7 @@ class _LinearBf16(torch.autograd.Function):
         if x.is_cuda:
             k = _k()
             out = torch.empty(B, N, device=x.device, dtype=out_dtype)
-            k.linear_bf16_fwd(xb.data_ptr(), wb.data_ptr(),
-                              b.data_ptr() if b is not None else 0,
+            k.linear_bf16_fwd(xb.data_ptr(), wb.data_ptr(), _ptr(b),
                               out.data_ptr(), B, K, N, fuse_relu,
                               out_dtype == torch.float32, _stream())
         else:
@@ -422,7 +428,7 @@ class _LinearBf16(torch.autograd.Function):
         gx = gw = gb = None
         if xb.is_cuda:
             k = _k()
-            mask = out.data_ptr() if out is not None else 0
+            mask = _ptr(out)
             mask_f32 = out is not None and out.dtype == torch.float32
             if need_x:
                 gx = torch.empty(B, K, device=xb.device, dtype=ctx.x_dtype)
@@ -440,8 +446,7 @@ class _LinearBf16(torch.autograd.Function):
                     if splits > 1 else None
                 k.linear_bf16_bwd_w(
                     gyb.data_ptr(), xb.data_ptr(), mask, mask_f32,
-                    gw.data_ptr(), gb.data_ptr() if gb is not None else 0,
-                    part.data_ptr() if part is not None else 0, splits,
+                    gw.data_ptr(), _ptr(gb), _ptr(part), splits,
                     B, K, N, _stream())
                 if ctx.w_dtype == torch.bfloat16:
                     gw = _to_bf16(gw)
@@ -532,8 +537,7 @@ class _Conv2dBf16(torch.autograd.Function):
         if x.is_cuda:
             out = torch.empty(B, K, OH, OW, device=x.device, dtype=out_dtype)
             _k().conv2d_bf16_fwd(
-                xb.data_ptr(), wb.data_ptr(),
-                b.data_ptr() if b is not None else 0, out.data_ptr(),
+                xb.data_ptr(), wb.data_ptr(), _ptr(b), out.data_ptr(),
                 B, C, H, W, K, R, S, sh, sw, ph, pw,
                 out_dtype == torch.float32, _stream())
         else:
@@ -576,10 +580,8 @@ class _Conv2dBf16(torch.autograd.Function):
                                    dtype=torch.float32) \
                     if splits > 1 else None
                 k.conv2d_bf16_bwd_w(
-                    gyb.data_ptr(), xb.data_ptr(), gw.data_ptr(),
-                    gb.data_ptr() if gb is not None else 0,
-                    part.data_ptr() if part is not None else 0, splits,
-                    *dims, _stream())
+                    gyb.data_ptr(), xb.data_ptr(), gw.data_ptr(), _ptr(gb),
+                    _ptr(part), splits, *dims, _stream())
                 if ctx.w_dtype == torch.bfloat16:
                     gw = _to_bf16(gw)
                 if not need_w:
@@ -687,12 +689,12 @@ def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
             splits = k.batchnorm2d_splits(B, C, H * W)
             ws = torch.empty(C * splits * 3, device=x.device,
                              dtype=torch.float32)
-        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         k.batchnorm2d_fwd(
-            x.data_ptr(), ptr(residual), y.data_ptr(), weight.data_ptr(),
-            bias.data_ptr(), ptr(running_mean), ptr(running_var), ptr(mean),
-            ptr(invstd), ptr(ws), splits, B, C, H * W, training, momentum,
-            eps, fuse_relu, x.dtype == torch.bfloat16, _stream())
+            x.data_ptr(), _ptr(residual), y.data_ptr(), weight.data_ptr(),
+            bias.data_ptr(), _ptr(running_mean), _ptr(running_var),
+            _ptr(mean), _ptr(invstd), _ptr(ws), splits, B, C, H * W,
+            training, momentum, eps, fuse_relu, x.dtype == torch.bfloat16,
+            _stream())
         return y, mean, invstd
     xf = x.float()
     if training:
@@ -755,12 +757,10 @@ class _BatchNorm2d(torch.autograd.Function):
             ws = torch.empty(C * splits * 2, device=x.device,
                              dtype=torch.float32)
             k.batchnorm2d_bwd(
-                x.data_ptr(), gy.data_ptr(),
-                y.data_ptr() if y is not None else 0, weight.data_ptr(),
+                x.data_ptr(), gy.data_ptr(), _ptr(y), weight.data_ptr(),
                 mean.data_ptr(), stat.data_ptr(), gw.data_ptr(),
-                gb.data_ptr(), gx.data_ptr() if gx is not None else 0,
-                gres.data_ptr() if gres is not None else 0, ws.data_ptr(),
-                splits, B, C, H * W, ctx.training, ctx.eps,
+                gb.data_ptr(), _ptr(gx), _ptr(gres), ws.data_ptr(), splits,
+                B, C, H * W, ctx.training, ctx.eps,
                 x.dtype == torch.bfloat16, _stream())
         else:
             inv = stat if ctx.training else 1.0 / torch.sqrt(stat + ctx.eps)
@@ -903,6 +903,7 @@ class _LogSoftmax(torch.autograd.Function):
 
 
 def log_softmax(x):
+    _require_fp32("log_softmax", x=x)
     return _LogSoftmax.apply(x.contiguous())
 
 
@@ -937,6 +938,7 @@ class _NllLoss(torch.autograd.Function):
 
 
 def nll_loss(logp, target):
+    _require_fp32("nll_loss", logp=logp)
     return _NllLoss.apply(logp.contiguous(), target.contiguous())
 
 
@@ -978,4 +980,5 @@ class _LogSoftmaxNll(torch.autograd.Function):
 
 
 def log_softmax_nll(logits, target):
+    _require_fp32("log_softmax_nll", logits=logits)
     return _LogSoftmaxNll.apply(logits.contiguous(), target.contiguous())
