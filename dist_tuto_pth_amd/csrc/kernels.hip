@@ -17,10 +17,11 @@
 //
 // This file also owns PYBIND11_MODULE; the pointwise ops (pointwise.hip),
 // the fused whole-Net step (net_fused.hip), the bf16 linear
-// (linear_bf16.hip), the bf16 convolution (conv_bf16.hip) and batch
-// normalization (batchnorm.hip) register their bindings through
-// register_pointwise() / register_net_fused() / register_linear_bf16() /
-// register_conv_bf16() / register_batchnorm().
+// (linear_bf16.hip), the bf16 convolution (conv_bf16.hip), batch
+// normalization (batchnorm.hip) and the general pooling ops (pool.hip)
+// register their bindings through register_pointwise() /
+// register_net_fused() / register_linear_bf16() / register_conv_bf16() /
+// register_batchnorm() / register_pool().
 
 #include "common.h"
 
@@ -843,6 +844,7 @@ void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
 void register_batchnorm(pybind11::module_& m);
+void register_pool(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
@@ -866,4 +868,5 @@ PYBIND11_MODULE(_kernels, m) {
   register_linear_bf16(m);
   register_conv_bf16(m);
   register_batchnorm(m);
+  register_pool(m);
 }

@@ -23,8 +23,10 @@ module's own weight, bias, running buffers, momentum and eps, with the
 ReLU fused into bn1 and bn2 and the residual add and final ReLU fused
 into bn3, so a block's tail is one kernel.  ``self.training`` selects
 batch or running statistics.  The classifier is ``ops.linear_bf16`` with
-fp32 logits.  Still borrowed from torch in this mode, on bf16 tensors: the
-stem's 3x3/2 max-pool and the global average pool.
+fp32 logits.  The stem's 3x3/2 max-pool is ``ops.maxpool2d`` with the
+``self.maxpool`` holder's kernel size, stride and padding, and the head's
+global average pool is ``ops.global_avgpool2d``, which already returns
+[B,C]: no op of this mode's forward or backward is borrowed from torch.
 ``num_batches_tracked`` is not touched: torch reads it only when
 ``momentum=None``, which ``ops.batchnorm2d`` does not support.
 """
@@ -142,9 +144,10 @@ class ResNet(nn.Module):
     def forward(self, x):
         if self.compute_dtype is not None:
             x = _bn(self.bn1, _conv_bf16(self.conv1, x), fuse_relu=True)
-            x = self.maxpool(x)
+            x = ops.maxpool2d(x, self.maxpool.kernel_size,
+                              self.maxpool.stride, self.maxpool.padding)
             x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-            x = self.avgpool(x).flatten(1)
+            x = ops.global_avgpool2d(x)
             return ops.linear_bf16(x, self.fc.weight, self.fc.bias,
                                    out_dtype=torch.float32)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))

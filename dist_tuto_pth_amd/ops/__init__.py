@@ -3,7 +3,7 @@
 Every op the reference's ``Net.forward`` + SGD step trigger implicitly
 through torch (train_dist.py:58-71,110,118-124) is a hand-written CDNA4
 HIP kernel here, with forward *and* backward (``csrc/kernels.hip``; K3-K6
-in ``csrc/pointwise.hip``, K16-K18 in the files named at their sections):
+in ``csrc/pointwise.hip``, K16-K20 in the files named at their sections):
 
   K1/K2  conv2d (direct, LDS-tiled)        -> conv2d
   K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu (fp32, bf16)
@@ -14,6 +14,9 @@ in ``csrc/pointwise.hip``, K16-K18 in the files named at their sections):
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
   K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d
+  K19    maxpool2d (kernel, stride, padding) -> maxpool2d (fp32, bf16)
+  K20    global average pool [B,C,H,W]->[B,C] -> global_avgpool2d
+                                              (fp32, bf16)
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
   K11-13 fused multi-tensor SGD+momentum   -> optim.FusedSGD
@@ -505,9 +508,9 @@ def linear_bf16(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
 _CONV_DIM_MAX = 2 ** 31 - 1 - 128   # the kernel's int GEMM dimensions
 
 
-def _pair(v, name, low):
+def _pair(v, name, low, op="conv2d_bf16"):
     if isinstance(v, bool):
-        raise ValueError(f"conv2d_bf16: {name} must be an int or a pair")
+        raise ValueError(f"{op}: {name} must be an int or a pair")
     if isinstance(v, int):
         v = (v, v)
     else:
@@ -515,13 +518,13 @@ def _pair(v, name, low):
             v = tuple(v)
         except TypeError:
             raise ValueError(
-                f"conv2d_bf16: {name} must be an int or a pair") from None
+                f"{op}: {name} must be an int or a pair") from None
     if len(v) != 2 or not all(isinstance(e, int) and not isinstance(e, bool)
                               for e in v):
-        raise ValueError(f"conv2d_bf16: {name} must be an int or a pair of "
+        raise ValueError(f"{op}: {name} must be an int or a pair of "
                          f"ints, got {v}")
     if min(v) < low:
-        raise ValueError(f"conv2d_bf16: {name} must be >= {low}, got {v}")
+        raise ValueError(f"{op}: {name} must be >= {low}, got {v}")
     return v
 
 
@@ -869,6 +872,162 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
         x.contiguous(), weight.contiguous(), bias.contiguous(), residual,
         running_mean, running_var, bool(training), float(momentum),
         float(eps), bool(fuse_relu))
+
+
+# ---------------------------------------------------------------------------
+# K19 — general max-pool over NCHW (kernel, stride, padding; windows may
+# overlap), fp32 or bf16 (csrc/pool.hip).  Contract, on GPU and CPU alike:
+# padding is -inf and never selected, the first maximum of a window wins a
+# tie, NaN propagates, the output carries the selected element's bits; the
+# backward sums, per input element and in fp32, the gradients of the windows
+# that selected it and rounds once.  No atomics: bitwise reproducible.
+# ---------------------------------------------------------------------------
+_POOL_MAX_PLANE = 2 ** 29     # the kernels' 32-bit in-plane indices
+_POOL_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _check_pool_input(op, x):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"ops.{op}: x must be a tensor")
+    if x.dtype not in _POOL_DTYPES:
+        raise TypeError(f"ops.{op}: x must be fp32 or bf16, got {x.dtype}")
+    if x.dim() != 4:
+        raise ValueError(f"ops.{op}: x [B,C,H,W] expected, got "
+                         f"{tuple(x.shape)}")
+    if min(x.shape) < 1:
+        raise ValueError(f"ops.{op}: every dimension must be >= 1, got "
+                         f"{tuple(x.shape)}")
+    if x.shape[2] * x.shape[3] > _POOL_MAX_PLANE:
+        raise ValueError(f"ops.{op}: H*W = {x.shape[2] * x.shape[3]} does "
+                         f"not fit the kernel's 32-bit plane index")
+
+
+class _MaxPool2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, stride, padding):
+        B, C, H, W = x.shape
+        (kh, kw), (sh, sw), (ph, pw) = kernel, stride, padding
+        ctx.geom = (B, C, H, W, kh, kw, sh, sw, ph, pw)
+        if x.is_cuda:
+            OH = (H + 2 * ph - kh) // sh + 1
+            OW = (W + 2 * pw - kw) // sw + 1
+            y = torch.empty(B, C, OH, OW, device=x.device, dtype=x.dtype)
+            slot = torch.empty(B, C, OH, OW, device=x.device,
+                               dtype=torch.uint8)
+            _k().maxpool2d_fwd(x.data_ptr(), y.data_ptr(), slot.data_ptr(),
+                               *ctx.geom, x.dtype == torch.bfloat16,
+                               _stream())
+            ctx.save_for_backward(slot)
+            return y
+        y, idx = F.max_pool2d(x, kernel, stride, padding,
+                              return_indices=True)
+        ctx.save_for_backward(idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (saved,) = ctx.saved_tensors
+        B, C, H, W = ctx.geom[:4]
+        gy = gy.contiguous()
+        if gy.is_cuda:
+            gx = torch.empty(B, C, H, W, device=gy.device,
+                             dtype=gy.dtype)      # fully written
+            _k().maxpool2d_bwd(gy.data_ptr(), saved.data_ptr(),
+                               gx.data_ptr(), *ctx.geom,
+                               gy.dtype == torch.bfloat16, _stream())
+            return gx, None, None, None
+        gx = torch.zeros(B * C, H * W, dtype=torch.float32)
+        gx.scatter_add_(1, saved.reshape(B * C, -1),
+                        gy.float().reshape(B * C, -1))
+        return gx.to(gy.dtype).view(B, C, H, W), None, None, None
+
+
+def maxpool2d(x, kernel_size, stride=None, padding=0):
+    """``max_pool2d(x, kernel_size, stride, padding)`` over NCHW.
+
+    ``x`` [B,C,H,W] is fp32 or bf16 and the result [B,C,OH,OW] has its
+    dtype, with ``OH = (H + 2*ph - kh)//sh + 1``.  ``kernel_size`` (>= 1),
+    ``stride`` (>= 1, ``None`` means ``kernel_size``) and ``padding``
+    (>= 0, at most half the kernel, torch's rule) are ints or (h, w) pairs;
+    ``kh*kw`` is at most 256 and windows may overlap.  No dilation,
+    ``ceil_mode`` or ``return_indices``.  Padding counts as -inf and is
+    never selected; the first maximum of a window (row-major) wins a tie,
+    a window of all -inf selects its first element and NaN propagates, as
+    in torch.  Max only selects, so the output carries the selected
+    element's bits and the bf16 result is the fp32 op's on the same values.
+    Backward gives ``gx`` in ``x``'s dtype: per input element the fp32 sum,
+    in a fixed order, of the gradients of the windows that selected it,
+    rounded once, and exact zeros elsewhere.  No atomics are used, so the
+    gradient of overlapping windows is bitwise reproducible."""
+    op = "ops.maxpool2d"
+    _check_pool_input("maxpool2d", x)
+    kh, kw = _pair(kernel_size, "kernel_size", 1, op)
+    sh, sw = (kh, kw) if stride is None else _pair(stride, "stride", 1, op)
+    ph, pw = _pair(padding, "padding", 0, op)
+    if ph > kh // 2 or pw > kw // 2:
+        raise ValueError(f"{op}: padding must be at most half the kernel "
+                         f"size, got padding {(ph, pw)} for kernel "
+                         f"{(kh, kw)}")
+    if kh * kw > 256:
+        raise ValueError(f"{op}: kernel_size {(kh, kw)} has more than 256 "
+                         f"positions")
+    H, W = x.shape[2:]
+    if H + 2 * ph < kh or W + 2 * pw < kw:
+        raise ValueError(f"{op}: a {kh}x{kw} window does not fit the padded "
+                         f"{H + 2 * ph}x{W + 2 * pw} input")
+    if max(sh, sw) > _POOL_MAX_PLANE:
+        raise ValueError(f"{op}: stride {(sh, sw)} does not fit the "
+                         f"kernel's 32-bit index")
+    return _MaxPool2d.apply(x.contiguous(), (kh, kw), (sh, sw), (ph, pw))
+
+
+# ---------------------------------------------------------------------------
+# K20 — global average pool [B,C,H,W] -> [B,C], fp32 or bf16
+# (csrc/pool.hip).  Contract, on GPU and CPU alike: each plane is summed in
+# fp32, divided once by H*W and rounded once to the output dtype.  The GPU
+# sum has a fixed order that depends on H*W alone, so it is bitwise
+# reproducible and independent of the pointer's alignment and of the dtype.
+# ---------------------------------------------------------------------------
+class _GlobalAvgPool2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        B, C, H, W = x.shape
+        ctx.in_shape = (B, C, H, W)
+        if x.is_cuda:
+            y = torch.empty(B, C, device=x.device, dtype=x.dtype)
+            _k().global_avgpool2d_fwd(x.data_ptr(), y.data_ptr(), B * C,
+                                      H * W, x.dtype == torch.bfloat16,
+                                      _stream())
+            return y
+        return (x.float().sum(dim=(2, 3)) / (H * W)).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, gy):
+        B, C, H, W = ctx.in_shape
+        gy = gy.contiguous()
+        if gy.is_cuda:
+            gx = torch.empty(B, C, H, W, device=gy.device,
+                             dtype=gy.dtype)      # fully written
+            _k().global_avgpool2d_bwd(gy.data_ptr(), gx.data_ptr(), B * C,
+                                      H * W, gy.dtype == torch.bfloat16,
+                                      _stream())
+            return gx
+        g = (gy.float() / (H * W)).to(gy.dtype)
+        return g.view(B, C, 1, 1).expand(B, C, H, W).contiguous()
+
+
+def global_avgpool2d(x):
+    """The mean of every plane: ``adaptive_avg_pool2d(x, 1).flatten(1)``.
+
+    ``x`` [B,C,H,W] is fp32 or bf16; the result is [B,C] in its dtype.
+    Each plane is summed in fp32, divided once by ``H*W`` and rounded once.
+    On the GPU the order of the sum is fixed by ``H*W`` alone: the result is
+    bitwise reproducible, a view at any element offset gives the bits of
+    its aligned copy, and the bf16 result is the fp32 op's on the same
+    values, rounded once.  Backward gives ``gx[b,c,:,:] = gy[b,c] / (H*W)``
+    in ``x``'s dtype, computed in fp32 and rounded once."""
+    _check_pool_input("global_avgpool2d", x)
+    return _GlobalAvgPool2d.apply(x.contiguous())
 
 
 # ---------------------------------------------------------------------------
