@@ -137,12 +137,15 @@ class _HipStreams:
 
 
 def _pad_chunks(tensor, size, buf):
-    """Return (work_flat, chunk, padded) with chunk aligned to 16 B."""
+    """Return (work_flat, chunk, padded) with chunk aligned to 16 B.  A
+    tensor that does not start on a 16-byte boundary (a view at an odd
+    offset) goes through the aligned work buffer as well: the reduction
+    launchers refuse a misaligned pointer."""
     flat = tensor.view(-1)
     n = flat.numel()
     align = 16 // flat.element_size()
     chunk = ((n + size - 1) // size + align - 1) // align * align
-    if chunk * size == n:
+    if chunk * size == n and flat.data_ptr() % 16 == 0:
         return flat, chunk, False
     work = buf(("pad", tensor.device.index, tensor.dtype), chunk * size,
                tensor.dtype, tensor.device)[:chunk * size]

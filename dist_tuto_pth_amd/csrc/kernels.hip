@@ -789,8 +789,20 @@ void sgd_step(const std::vector<uintptr_t>& ps,
 }
 
 
+// The reduction kernels move 16 bytes per access and divide the row
+// stride by the vector width: a pointer or stride that breaks either
+// would give wrong sums silently, so the launchers refuse it.
+void require_aligned16(const char* op, const char* name, uintptr_t p) {
+  if (p % 16 != 0)
+    throw std::invalid_argument(std::string(op) + ": " + name +
+                                " must be 16-byte aligned");
+}
+
 void add_inplace(uintptr_t dst, uintptr_t src, int64_t n, int dtype,
                  uintptr_t stream) {
+  if (n < 0) throw std::invalid_argument("add_inplace: n must be >= 0");
+  require_aligned16("add_inplace", "dst", dst);
+  require_aligned16("add_inplace", "src", src);
   if (dtype == 7) {  // ncclFloat32 numbering (dist wrapper's _DTYPE)
     hipLaunchKernelGGL(add_inplace_f32_kernel, dim3(grid_for(n, BLK, 4)),
                        dim3(BLK), 0, S(stream), (float*)dst,
@@ -806,6 +818,17 @@ void add_inplace(uintptr_t dst, uintptr_t src, int64_t n, int dtype,
 
 void reduce_columns(uintptr_t dst, uintptr_t src, int P, int64_t stride,
                     int64_t n, double scale, int dtype, uintptr_t stream) {
+  if (n < 0 || P < 0)
+    throw std::invalid_argument("reduce_columns: n and P must be >= 0");
+  require_aligned16("reduce_columns", "dst", dst);
+  if (P > 0) {  // P == 0 only scales dst and never reads src
+    const int64_t vec = dtype == 7 ? 4 : 8;
+    if (stride < 0 || stride % vec != 0)
+      throw std::invalid_argument(
+          "reduce_columns: stride must be a multiple of " +
+          std::to_string(vec) + " elements, got " + std::to_string(stride));
+    require_aligned16("reduce_columns", "src", src);
+  }
   if (dtype == 7) {
     hipLaunchKernelGGL(reduce_columns_f32_kernel,
                        dim3(grid_for(n, BLK, 4)), dim3(BLK), 0, S(stream),
@@ -822,6 +845,8 @@ void reduce_columns(uintptr_t dst, uintptr_t src, int P, int64_t stride,
 }
 
 void scale_f32(uintptr_t dst, double s, int64_t n, uintptr_t stream) {
+  if (n < 0) throw std::invalid_argument("scale_f32: n must be >= 0");
+  require_aligned16("scale_f32", "dst", dst);
   hipLaunchKernelGGL(scale_f32_kernel, dim3(grid_for(n, BLK, 4)), dim3(BLK),
                      0, S(stream), (float*)dst, (float)s, n);
 }

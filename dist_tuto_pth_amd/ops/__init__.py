@@ -60,6 +60,54 @@ def _require_fp32(op, hint="", **tensors):
                             f"dtype {t.dtype}{hint}")
 
 
+_INT_MAX = 2 ** 31 - 1   # the fp32 kernels index weights and planes in int
+
+
+def _require_tensors(op, **tensors):
+    for name, t in tensors.items():
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"ops.{op}: {name} must be a tensor")
+
+
+def _require_same_device(op, x, **others):
+    for name, t in others.items():
+        if t is not None and t.device != x.device:
+            raise ValueError(f"ops.{op}: {name} is on {t.device}, the input "
+                             f"on {x.device}")
+
+
+def _require_fits_int(op, **sizes):
+    for what, v in sizes.items():
+        if v > _INT_MAX:
+            raise ValueError(f"ops.{op}: {what} = {v} does not fit the "
+                             f"kernel's 32-bit index")
+
+
+def _check_rows(op, name, x):
+    """``x`` is the [B,N] matrix of a row-wise op."""
+    if x.dim() != 2:
+        raise ValueError(f"ops.{op}: {name} [B,N] expected, got "
+                         f"{tuple(x.shape)}")
+    if min(x.shape) < 1:
+        raise ValueError(f"ops.{op}: B and N must be >= 1, got "
+                         f"{tuple(x.shape)}")
+    _require_fits_int(op, B=x.shape[0], N=x.shape[1])
+
+
+def _check_target(op, x, target):
+    """``target`` holds one int64 class index per row of ``x``.  Its values
+    stay unchecked: reading them would synchronize with the device, which
+    a captured graph forbids."""
+    _require_tensors(op, target=target)
+    if target.dtype != torch.int64:
+        raise TypeError(f"ops.{op}: target must be int64, got "
+                        f"{target.dtype}")
+    if target.shape != (x.shape[0],):
+        raise ValueError(f"ops.{op}: target must have shape "
+                         f"[{x.shape[0]}], got {tuple(target.shape)}")
+    _require_same_device(op, x, target=target)
+
+
 # ---------------------------------------------------------------------------
 # K1/K2 — direct convolution (no padding, stride 1: the only form Net uses)
 # ---------------------------------------------------------------------------
@@ -86,8 +134,9 @@ class _Conv2d(torch.autograd.Function):
             k = _k()
             B, C, H, W = x.shape
             K, _, R, S = w.shape
-            gx = torch.empty_like(x)
-            gw = torch.empty_like(w)   # fully written by the kernel
+            # fully written by the kernels, in dense order
+            gx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+            gw = torch.empty(w.shape, device=x.device, dtype=x.dtype)
             gb = torch.empty(K, device=x.device, dtype=x.dtype) \
                 if ctx.needs_input_grad[2] else None
             k.conv2d_bwd(x.data_ptr(), w.data_ptr(), gy.data_ptr(),
@@ -101,8 +150,33 @@ class _Conv2d(torch.autograd.Function):
 
 
 def conv2d(x, w, b=None):
+    """Valid cross-correlation, stride 1: ``x`` [B,C,H,W], ``w`` [K,C,R,S]
+    and ``b`` [K] or None, fp32 on GPU, in any memory layout (the kernels
+    read dense copies and return dense gradients)."""
+    _require_tensors("conv2d", x=x, w=w, b=b)
     _require_fp32("conv2d", x=x, w=w, b=b)
-    return _Conv2d.apply(x.contiguous(), w, b)
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(f"ops.conv2d: x [B,C,H,W] and w [K,C,R,S] expected, "
+                         f"got {tuple(x.shape)} and {tuple(w.shape)}")
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"ops.conv2d: x has {x.shape[1]} channels, w "
+                         f"expects {w.shape[1]}")
+    if min(x.shape) < 1 or min(w.shape) < 1:
+        raise ValueError("ops.conv2d: every dimension must be >= 1")
+    if b is not None and b.shape != (w.shape[0],):
+        raise ValueError(f"ops.conv2d: b must have shape [{w.shape[0]}], "
+                         f"got {tuple(b.shape)}")
+    B, C, H, W = x.shape
+    K, _, R, S = w.shape
+    if R > H or S > W:
+        raise ValueError(f"ops.conv2d: a {R}x{S} filter does not fit the "
+                         f"{H}x{W} input")
+    _require_same_device("conv2d", x, w=w, b=b)
+    _require_fits_int("conv2d", **{"B": B, "C*H*W": C * H * W,
+                                   "K*C*R*S": K * C * R * S,
+                                   "K*OH*OW": K * (H - R + 1) * (W - S + 1)})
+    return _Conv2d.apply(x.contiguous(), w.contiguous(),
+                         None if b is None else b.contiguous())
 
 
 # ---------------------------------------------------------------------------
@@ -349,8 +423,9 @@ class _Linear(torch.autograd.Function):
             k = _k()
             B, K = x.shape
             N = w.shape[0]
-            gx = torch.empty_like(x)
-            gw = torch.empty_like(w)
+            # fully written by the kernels, in dense order
+            gx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+            gw = torch.empty(w.shape, device=x.device, dtype=x.dtype)
             gb = torch.empty(N, device=x.device, dtype=x.dtype) \
                 if ctx.has_bias else None
             k.linear_bwd(x.data_ptr(), w.data_ptr(), gy.data_ptr(),
@@ -367,9 +442,29 @@ class _Linear(torch.autograd.Function):
 
 
 def linear(x, w, b=None, fuse_relu=False):
+    """``relu?(x @ w.T + b)``: ``x`` [B,K], ``w`` [N,K] and ``b`` [N] or
+    None, fp32 on GPU, in any memory layout (the kernels read dense copies
+    and return dense gradients)."""
+    _require_tensors("linear", x=x, w=w, b=b)
     _require_fp32("linear", "; use ops.linear_bf16 for bf16 operands",
                   x=x, w=w, b=b)
-    return _Linear.apply(x.contiguous(), w, b, fuse_relu)
+    if x.dim() != 2 or w.dim() != 2:
+        raise ValueError(f"ops.linear: x [B,K] and w [N,K] expected, got "
+                         f"{tuple(x.shape)} and {tuple(w.shape)}")
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"ops.linear: x has K = {x.shape[1]}, w expects "
+                         f"{w.shape[1]}")
+    if min(x.shape) < 1 or w.shape[0] < 1:
+        raise ValueError("ops.linear: B, K and N must be >= 1")
+    if b is not None and b.shape != (w.shape[0],):
+        raise ValueError(f"ops.linear: b must have shape [{w.shape[0]}], "
+                         f"got {tuple(b.shape)}")
+    _require_same_device("linear", x, w=w, b=b)
+    _require_fits_int("linear", **{"B": x.shape[0],
+                                   "N*K": w.shape[0] * w.shape[1]})
+    return _Linear.apply(x.contiguous(), w.contiguous(),
+                         None if b is None else b.contiguous(),
+                         bool(fuse_relu))
 
 
 # ---------------------------------------------------------------------------
@@ -1062,7 +1157,10 @@ class _LogSoftmax(torch.autograd.Function):
 
 
 def log_softmax(x):
+    """``log_softmax(x, dim=1)`` of ``x`` [B,N], fp32 on GPU."""
+    _require_tensors("log_softmax", x=x)
     _require_fp32("log_softmax", x=x)
+    _check_rows("log_softmax", "x", x)
     return _LogSoftmax.apply(x.contiguous())
 
 
@@ -1097,7 +1195,14 @@ class _NllLoss(torch.autograd.Function):
 
 
 def nll_loss(logp, target):
+    """Mean of ``-logp[b, target[b]]`` over ``logp`` [B,N] (fp32 on GPU)
+    and an int64 ``target`` [B].  A target value outside ``[0, N)`` is not
+    checked: reading it would synchronize with the device, which a
+    captured graph forbids."""
+    _require_tensors("nll_loss", logp=logp)
     _require_fp32("nll_loss", logp=logp)
+    _check_rows("nll_loss", "logp", logp)
+    _check_target("nll_loss", logp, target)
     return _NllLoss.apply(logp.contiguous(), target.contiguous())
 
 
@@ -1139,5 +1244,12 @@ class _LogSoftmaxNll(torch.autograd.Function):
 
 
 def log_softmax_nll(logits, target):
+    """``nll_loss(log_softmax(logits), target)`` in one kernel, for
+    ``logits`` [B,N] (fp32 on GPU) and an int64 ``target`` [B].  A target
+    value outside ``[0, N)`` is not checked: reading it would synchronize
+    with the device, which a captured graph forbids."""
+    _require_tensors("log_softmax_nll", logits=logits)
     _require_fp32("log_softmax_nll", logits=logits)
+    _check_rows("log_softmax_nll", "logits", logits)
+    _check_target("log_softmax_nll", logits, target)
     return _LogSoftmaxNll.apply(logits.contiguous(), target.contiguous())

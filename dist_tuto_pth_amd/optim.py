@@ -20,6 +20,29 @@ import torch
 from .utils.native import load_native
 
 
+def _require_dense_fp32(i, p, grad, buf):
+    """The kernel walks parameter, gradient and momentum buffer as flat
+    fp32 arrays of ``p.numel()`` elements: refuse anything else before its
+    pointer reaches it."""
+    for name, t in (("parameter", p), ("gradient", grad),
+                    ("momentum buffer", buf)):
+        if t is None:
+            continue
+        if t.device != p.device or not t.is_cuda:
+            raise ValueError(f"FusedSGD.step: {name} {i} is on {t.device}, "
+                             f"its parameter on {p.device}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"FusedSGD.step is fp32 only on GPU, got "
+                            f"{name} {i} of dtype {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"FusedSGD.step: {name} {i} must be "
+                             f"contiguous, got strides {t.stride()}")
+        if t.shape != p.shape:
+            raise ValueError(f"FusedSGD.step: {name} {i} has shape "
+                             f"{tuple(t.shape)}, its parameter "
+                             f"{tuple(p.shape)}")
+
+
 class FusedSGD:
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 0.01,
                  momentum: float = 0.0, zero_grad_in_step: bool = False):
@@ -41,10 +64,11 @@ class FusedSGD:
             for i, p in enumerate(self.params):
                 if p.grad is None:
                     continue
+                buf = self._bufs[i] if self._bufs is not None else None
+                _require_dense_fp32(i, p, p.grad, buf)
                 ptrs_p.append(p.data_ptr())
                 ptrs_g.append(p.grad.data_ptr())
-                ptrs_b.append(self._bufs[i].data_ptr()
-                              if self._bufs is not None else 0)
+                ptrs_b.append(buf.data_ptr() if buf is not None else 0)
                 numels.append(p.numel())
             k.sgd_step(ptrs_p, ptrs_g, ptrs_b, numels, self.lr,
                        self.momentum, self.zero_grad_in_step,

@@ -13,7 +13,9 @@ covered by tests/test_rccl_gpu.py on the GPU box.
 """
 
 import ctypes
+import os
 import queue
+import sys
 import threading
 
 import numpy as np
@@ -23,6 +25,9 @@ import torch
 from dist_tuto_pth_amd.algorithms.xgmi import (_sub_splits,
                                                fullmesh_all_reduce,
                                                ring_all_reduce)
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fp32_bounds as fb  # noqa: E402
 
 # ---------------------------------------------------------------------------
 # fakes
@@ -97,49 +102,31 @@ def _u16(ptr, n):
         ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint16)), shape=(n,))
 
 
-def _bf16_to_f32(u16arr):
-    return torch.from_numpy(u16arr.copy()).view(torch.bfloat16) \
-        .float().numpy()
-
-
-def _f32_to_bf16(f32arr):
-    return torch.from_numpy(np.ascontiguousarray(f32arr, dtype=np.float32)) \
-        .bfloat16().view(torch.uint16).numpy()
+def _tensor(ptr, n, dt):
+    """The ``n`` elements at ``ptr`` as a torch tensor sharing the memory."""
+    if dt == 7:
+        return torch.from_numpy(_f32(ptr, n))
+    if dt == 9:
+        return torch.from_numpy(_u16(ptr, n)).view(torch.bfloat16)
+    raise ValueError(dt)
 
 
 class FakeKernels:
-    """ctypes/numpy reimplementation of the reduction kernels' CONTRACT
-    (csrc/kernels.hip): reduce_columns accumulates fp32 and rounds
-    once; add_inplace is an elementwise add."""
+    """The reduction kernels' CONTRACT (csrc/kernels.hip) on raw host
+    pointers: reduce_columns accumulates fp32 and rounds once; add_inplace
+    is an elementwise add.  The arithmetic is tests/fp32_bounds.py's
+    contract model, the one tests/test_fp32_kernels_gpu.py holds the real
+    kernels to, bit for bit."""
 
     def reduce_columns(self, dst, src, P, stride, n, scale, dt, stream):
-        if dt == 7:
-            d = _f32(dst, n)
-            acc = d.copy()
-            for p in range(P):
-                acc += _f32(src + p * stride * 4, n)
-            d[:] = acc * np.float32(scale)
-        elif dt == 9:
-            dv = _u16(dst, n)
-            acc = _bf16_to_f32(dv)
-            for p in range(P):
-                acc += _bf16_to_f32(_u16(src + p * stride * 2, n))
-            dv[:] = _f32_to_bf16(acc * np.float32(scale))
-        else:
-            raise ValueError(dt)
+        s = _tensor(src, (P - 1) * stride + n, dt) if P > 0 else None
+        fb.reduce_columns_model(_tensor(dst, n, dt), s, P, stride, n, scale)
 
     def add_inplace(self, dst, src, n, dt, stream):
-        if dt == 7:
-            _f32(dst, n)[:] += _f32(src, n)
-        elif dt == 9:
-            dv = _u16(dst, n)
-            dv[:] = _f32_to_bf16(_bf16_to_f32(dv) +
-                                 _bf16_to_f32(_u16(src, n)))
-        else:
-            raise ValueError(dt)
+        fb.add_inplace_model(_tensor(dst, n, dt), _tensor(src, n, dt), n)
 
     def scale_f32(self, dst, scale, n, stream):
-        _f32(dst, n)[:] *= np.float32(scale)
+        fb.scale_f32_model(_tensor(dst, n, 7), scale, n)
 
 
 def _per_rank_buf():
