@@ -19,8 +19,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from dist_tuto_pth_amd import dist  # noqa: E402
+from dist_tuto_pth_amd import dist, ops  # noqa: E402
 from dist_tuto_pth_amd.models.resnet import resnet50  # noqa: E402
+from dist_tuto_pth_amd.optim import FusedSGD  # noqa: E402
 from dist_tuto_pth_amd.parallel.ddp import DistributedDataParallel  # noqa: E402
 
 
@@ -49,8 +50,15 @@ def main():
                    help="build the model with compute_dtype=bfloat16: "
                         "convs, BN and the classifier on this package's "
                         "own HIP ops; autocast and channels_last are off")
+    p.add_argument("--own-step", action="store_true",
+                   help="with --compute-dtype bf16: the loss is "
+                        "ops.cross_entropy and the optimizer FusedSGD "
+                        "(same lr and momentum), so nothing of the step is "
+                        "borrowed from torch")
     args = p.parse_args()
     own_bf16 = args.compute_dtype == "bf16"
+    if args.own_step and not own_bf16:
+        p.error("--own-step needs --compute-dtype bf16")
     if own_bf16:
         args.channels_last = False
         args.dtype = "fp32"      # no autocast: the model casts itself
@@ -83,21 +91,35 @@ def main():
     if (world > 1 or args.force_comm) and not args.no_overlap:
         ddp = DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb,
                                       force_comm=args.force_comm)
-    opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9)
+    if args.own_step:
+        opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9)
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9)
 
     g = torch.Generator().manual_seed(1234 + rank)
     x = torch.randn(args.batch, 3, 224, 224, generator=g).to(device)
     if args.channels_last:
         x = x.to(memory_format=torch.channels_last)
     tgt = torch.randint(0, 1000, (args.batch,), generator=g).to(device)
-    crit = torch.nn.CrossEntropyLoss()
+    crit = ops.cross_entropy if args.own_step \
+        else torch.nn.CrossEntropyLoss()
 
     import contextlib
     amp = (torch.autocast("cuda", dtype=torch.bfloat16)
            if args.dtype == "bf16" else contextlib.nullcontext())
 
+    def clear_grads():
+        if args.own_step:
+            # FusedSGD.step skips a parameter without a gradient, and
+            # autograd stores into an empty .grad instead of adding to it:
+            # no zeroing pass, as zero_grad(set_to_none=True) does for torch
+            for prm in opt.params:
+                prm.grad = None
+        else:
+            opt.zero_grad(set_to_none=True)
+
     def step():
-        opt.zero_grad(set_to_none=True)
+        clear_grads()
         if ddp is not None:
             with amp:
                 loss = crit(ddp(x), tgt)
@@ -146,6 +168,9 @@ def main():
             "dtype": "bf16 (compute_dtype, own HIP ops)" if own_bf16
             else args.dtype,
             "data": "synthetic",
+            "loss": "ops.cross_entropy" if args.own_step
+            else "torch.nn.CrossEntropyLoss",
+            "optimizer": "FusedSGD" if args.own_step else "torch.optim.SGD",
             "config": {"model": "ResNet-50", "global_batch":
                        args.batch * world, "input": "3x224x224",
                        "parallelism": f"dp{world}",

@@ -50,7 +50,8 @@ def build(force: bool = False):
         ("_rcclx.so", src("rcclx.cpp"), [], ["-L/opt/rocm/lib", "-lrccl"]),
         ("_kernels.so", src("kernels.hip", "pointwise.hip", "net_fused.hip",
                             "linear_bf16.hip", "conv_bf16.hip",
-                            "batchnorm.hip", "pool.hip"),
+                            "batchnorm.hip", "pool.hip",
+                            "cross_entropy.hip"),
          src("common.h", "gemm_bf16.h"), []),
     ]
     for out_name, srcs, hdrs, extra in targets:

@@ -21,7 +21,8 @@
 // normalization (batchnorm.hip) and the general pooling ops (pool.hip)
 // register their bindings through register_pointwise() /
 // register_net_fused() / register_linear_bf16() / register_conv_bf16() /
-// register_batchnorm() / register_pool().
+// register_batchnorm() / register_pool(); the cross-entropy loss
+// (cross_entropy.hip) through register_cross_entropy().
 
 #include "common.h"
 
@@ -419,6 +420,10 @@ __global__ void log_softmax_nll_bwd_kernel(const float* __restrict__ logp,
 // K11-K13 — fused multi-tensor SGD+momentum: buf = mu*buf + g;
 // p -= lr*buf; optionally g = 0 (K12 folded in).  All of Net's 8
 // tensors in ONE launch: pointer table passed by value.
+// Two compile-time options follow torch's rule: weight decay (WD) takes
+// g' = g + wd*p for g, Nesterov momentum (NEST) steps along g' + mu*buf
+// instead of buf.  The <false, false> instance is the arithmetic above and
+// nothing else.
 // ===========================================================================
 #define MT_MAX 32
 struct MtArgs {
@@ -431,7 +436,8 @@ struct MtArgs {
   int64_t total;
 };
 
-__global__ void sgd_step_kernel(MtArgs a, float lr, float mu,
+template <bool WD, bool NEST>
+__global__ void sgd_step_kernel(MtArgs a, float lr, float mu, float wd,
                                 int zero_grad) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < a.total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -443,7 +449,13 @@ __global__ void sgd_step_kernel(MtArgs a, float lr, float mu,
     }
     const int64_t j = i - a.offset[lo];
     float g = a.g[lo][j];
-    if (a.buf[lo]) {
+    if (WD) g = g + wd * a.p[lo][j];
+    if (NEST) {
+      // the wrapper refuses Nesterov without momentum: buf is never null
+      const float b = mu * a.buf[lo][j] + g;
+      a.buf[lo][j] = b;
+      g = g + mu * b;
+    } else if (a.buf[lo]) {
       g = mu * a.buf[lo][j] + g;
       a.buf[lo][j] = g;
     }
@@ -765,7 +777,23 @@ void sgd_step(const std::vector<uintptr_t>& ps,
               const std::vector<uintptr_t>& gs,
               const std::vector<uintptr_t>& bufs,
               const std::vector<int64_t>& numels, double lr, double mu,
-              bool zero_grad, uintptr_t stream) {
+              bool zero_grad, uintptr_t stream, double weight_decay,
+              bool nesterov) {
+  if (weight_decay < 0)
+    throw std::invalid_argument("sgd_step: weight_decay must be >= 0");
+  if (nesterov) {
+    if (mu == 0)
+      throw std::invalid_argument("sgd_step: nesterov needs momentum");
+    for (uintptr_t b : bufs)
+      if (!b)
+        throw std::invalid_argument(
+            "sgd_step: nesterov needs a momentum buffer per tensor");
+  }
+  const bool wd = weight_decay != 0;
+  auto kernel = nesterov ? (wd ? sgd_step_kernel<true, true>
+                               : sgd_step_kernel<false, true>)
+                         : (wd ? sgd_step_kernel<true, false>
+                               : sgd_step_kernel<false, false>);
   size_t i = 0;
   while (i < ps.size()) {
     MtArgs a{};
@@ -782,9 +810,9 @@ void sgd_step(const std::vector<uintptr_t>& ps,
       ++a.count;
       ++i;
     }
-    hipLaunchKernelGGL(sgd_step_kernel, dim3(grid_for(a.total, BLK)),
-                       dim3(BLK), 0, S(stream), a, (float)lr, (float)mu,
-                       zero_grad ? 1 : 0);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(a.total, BLK)), dim3(BLK), 0,
+                       S(stream), a, (float)lr, (float)mu,
+                       (float)weight_decay, zero_grad ? 1 : 0);
   }
 }
 
@@ -863,13 +891,15 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 // pointwise.hip, the fused whole-Net step in net_fused.hip, K16 (bf16 MFMA
 // linear) in linear_bf16.hip, K17 (bf16 MFMA convolution) in
 // conv_bf16.hip, K18 (batch normalization with fused add and ReLU) in
-// batchnorm.hip
+// batchnorm.hip, K19/K20 (general pooling) in pool.hip, K21 (cross-entropy
+// for wide rows) in cross_entropy.hip
 void register_pointwise(pybind11::module_& m);
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
 void register_batchnorm(pybind11::module_& m);
 void register_pool(pybind11::module_& m);
+void register_cross_entropy(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
   m.doc() = "CDNA4 HIP kernels for the dist_tuto_pth_amd training path";
@@ -883,7 +913,15 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("nll_loss_bwd", &nll_loss_bwd);
   m.def("log_softmax_nll_fwd", &log_softmax_nll_fwd);
   m.def("log_softmax_nll_bwd", &log_softmax_nll_bwd);
-  m.def("sgd_step", &sgd_step);
+  {
+    namespace py = pybind11;
+    // weight_decay and nesterov trail with defaults: the earlier
+    // positional call keeps working
+    m.def("sgd_step", &sgd_step, py::arg("ps"), py::arg("gs"),
+          py::arg("bufs"), py::arg("numels"), py::arg("lr"), py::arg("mu"),
+          py::arg("zero_grad"), py::arg("stream"),
+          py::arg("weight_decay") = 0.0, py::arg("nesterov") = false);
+  }
   m.def("add_inplace", &add_inplace);
   m.def("copy_throttled", &copy_throttled);
   m.def("reduce_columns", &reduce_columns);
@@ -894,4 +932,5 @@ PYBIND11_MODULE(_kernels, m) {
   register_conv_bf16(m);
   register_batchnorm(m);
   register_pool(m);
+  register_cross_entropy(m);
 }

@@ -3,7 +3,7 @@
 Every op the reference's ``Net.forward`` + SGD step trigger implicitly
 through torch (train_dist.py:58-71,110,118-124) is a hand-written CDNA4
 HIP kernel here, with forward *and* backward (``csrc/kernels.hip``; K3-K6
-in ``csrc/pointwise.hip``, K16-K20 in the files named at their sections):
+in ``csrc/pointwise.hip``, K16-K21 in the files named at their sections):
 
   K1/K2  conv2d (direct, LDS-tiled)        -> conv2d
   K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu (fp32, bf16)
@@ -19,6 +19,8 @@ in ``csrc/pointwise.hip``, K16-K20 in the files named at their sections):
                                               (fp32, bf16)
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
+  K21    cross-entropy for wide rows (label   -> cross_entropy (fp32, bf16)
+         smoothing, ignore_index, reduction)
   K11-13 fused multi-tensor SGD+momentum   -> optim.FusedSGD
 
 Dispatch: GPU tensors REQUIRE the native extension (loud failure, no
@@ -1253,3 +1255,151 @@ def log_softmax_nll(logits, target):
     _check_rows("log_softmax_nll", "logits", logits)
     _check_target("log_softmax_nll", logits, target)
     return _LogSoftmaxNll.apply(logits.contiguous(), target.contiguous())
+
+
+# ---------------------------------------------------------------------------
+# K21 — cross-entropy over [B,N] logits, fp32 or bf16, for rows of any
+# width (csrc/cross_entropy.hip).  Contract, on GPU and CPU alike: all
+# arithmetic is fp32 and the loss is fp32 whatever the logits' dtype.  With
+# eps = label_smoothing and t = target[b],
+#     row[b]  = lse[b] - (1-eps)*x[b,t] - (eps/N)*sum_i x[b,i]
+#     gx[b,i] = (exp(x[b,i] - lse[b]) - q[b,i]) * g,
+#               q = (1-eps)*onehot + eps/N
+# where the smoothing term is left out for eps == 0 (a -inf logit then gives
+# p = 0 and a finite loss).  A row with t == ignore_index contributes 0 and
+# its gx row is stored zeros; "mean" divides by the number of rows not
+# ignored, taken on the device (0 rows give NaN, as in torch).  g is the
+# upstream gradient, divided by that count for "mean".  The forward saves
+# lse [B] and the count, never a [B,N] tensor; the backward recomputes the
+# softmax from the logits and rounds gx once to their dtype.  No float
+# atomics: every result is bitwise reproducible.
+# ---------------------------------------------------------------------------
+_XENT_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _cross_entropy_cpu_forward(xf, target, eps, ignore_index):
+    """Row losses, lse and the keep mask of the contract, in plain fp32
+    torch.  The target is only compared with the column index."""
+    B, N = xf.shape
+    m = xf.max(dim=1, keepdim=True).values
+    lse = (m + torch.log(torch.exp(xf - m).sum(dim=1, keepdim=True)))[:, 0]
+    keep = target != ignore_index
+    onehot = torch.arange(N)[None, :] == target[:, None]
+    x_t = torch.where(onehot, xf, torch.zeros_like(xf)).sum(dim=1)
+    row = lse - (1.0 - eps) * x_t
+    if eps != 0.0:
+        row = row - (eps / N) * xf.sum(dim=1)
+    zero = torch.zeros_like(row)
+    return torch.where(keep, row, zero), torch.where(keep, lse, zero), keep
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, eps, ignore_index, reduction):
+        B, N = logits.shape
+        red = _XENT_REDUCTIONS[reduction]
+        ctx.meta = (eps, ignore_index, red)
+        f32 = dict(device=logits.device, dtype=torch.float32)
+        if logits.is_cuda:
+            row = torch.empty(B, **f32)
+            lse = torch.empty(B, **f32)
+            loss = count = None
+            if red:
+                loss = torch.empty((), **f32)
+                count = torch.empty(1, **f32)
+            _k().cross_entropy_fwd(
+                logits.data_ptr(), target.data_ptr(), row.data_ptr(),
+                lse.data_ptr(), _ptr(loss), _ptr(count), B, N, eps,
+                ignore_index, red, logits.dtype == torch.bfloat16, 0,
+                _stream())
+            ctx.save_for_backward(logits, target, lse, count)
+            return loss if red else row
+        row, lse, keep = _cross_entropy_cpu_forward(
+            logits.float(), target, eps, ignore_index)
+        count = keep.sum().to(torch.float32).reshape(1)
+        ctx.save_for_backward(logits, target, lse, count)
+        if red == 0:
+            return row
+        return row.sum() / count[0] if red == 1 else row.sum()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        logits, target, lse, count = ctx.saved_tensors
+        eps, ignore_index, red = ctx.meta
+        B, N = logits.shape
+        gl = gloss.contiguous().float()
+        if logits.is_cuda:
+            gx = torch.empty_like(logits)       # fully written
+            _k().cross_entropy_bwd(
+                logits.data_ptr(), target.data_ptr(), lse.data_ptr(),
+                _ptr(count), gl.data_ptr(), gx.data_ptr(), B, N, eps,
+                ignore_index, red, logits.dtype == torch.bfloat16, 0,
+                _stream())
+            return gx, None, None, None, None
+        xf = logits.float()
+        keep = (target != ignore_index)[:, None]
+        onehot = torch.arange(N)[None, :] == target[:, None]
+        en = torch.tensor(eps, dtype=torch.float32) / N
+        q = torch.where(onehot, (1.0 - eps) + en, en)
+        if red == 0:
+            g = gl[:, None]
+        else:
+            g = gl / count[0] if red == 1 else gl
+        gx = (torch.exp(xf - lse[:, None]) - q) * g
+        # stored zeros, never 0 * g
+        gx = torch.where(keep, gx, torch.zeros_like(gx))
+        return gx.to(logits.dtype), None, None, None, None
+
+
+def cross_entropy(logits, target, *, label_smoothing=0.0, ignore_index=-100,
+                  reduction="mean"):
+    """Cross-entropy of ``logits`` [B,N] (fp32 or bf16) against an int64
+    ``target`` [B] of class indices, for rows of any width.
+
+    The result is fp32 whatever the logits' dtype: a scalar for
+    ``reduction`` ``"mean"`` or ``"sum"``, [B] for ``"none"``.  With
+    ``eps = label_smoothing`` in [0, 1] the row loss is
+    ``lse - (1-eps)*x[t] - (eps/N)*sum(x)``; a row whose target equals
+    ``ignore_index`` contributes 0 and gets an all-zero gradient row, and
+    ``"mean"`` divides by the number of rows not ignored (NaN when there
+    are none, as in torch).  That count is taken on the device, so the op
+    can be captured in a graph.  Backward gives ``gx`` in the logits'
+    dtype, ``(softmax(x) - q) * g`` with ``q = (1-eps)*onehot + eps/N``,
+    computed in fp32 from the saved log-sum-exp and rounded once; nothing
+    of size [B,N] is saved.  No atomics: loss and gradient are bitwise
+    reproducible, do not depend on the pointer's alignment, and the bf16
+    row losses are those of the fp32 op on the same values.
+
+    Not supported: class weights, probability (soft) targets and logits of
+    more than two dimensions.  A target value outside ``[0, N)`` that is
+    not ``ignore_index`` is not checked, because reading it would
+    synchronize with the device; the GPU kernels only compare it with the
+    column index, so it gives a meaningless loss but no out-of-bounds
+    access."""
+    op = "cross_entropy"
+    _require_tensors(op, logits=logits)
+    if logits.is_cuda and logits.dtype not in (torch.float32,
+                                               torch.bfloat16):
+        raise TypeError(f"ops.{op}: fp32 or bf16 logits only on GPU, got "
+                        f"{logits.dtype}")
+    if not logits.is_floating_point():
+        raise TypeError(f"ops.{op}: logits must be floating point, got "
+                        f"{logits.dtype}")
+    _check_rows(op, "logits", logits)
+    _check_target(op, logits, target)
+    if isinstance(label_smoothing, bool) \
+            or not isinstance(label_smoothing, (int, float)) \
+            or not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"ops.{op}: label_smoothing must be a real number "
+                         f"in [0, 1], got {label_smoothing!r}")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise TypeError(f"ops.{op}: ignore_index must be an int, got "
+                        f"{ignore_index!r}")
+    if not -2 ** 63 <= ignore_index < 2 ** 63:
+        raise ValueError(f"ops.{op}: ignore_index does not fit int64")
+    if reduction not in _XENT_REDUCTIONS:
+        raise ValueError(f"ops.{op}: reduction must be 'none', 'mean' or "
+                         f"'sum', got {reduction!r}")
+    return _CrossEntropy.apply(logits.contiguous(), target.contiguous(),
+                               float(label_smoothing), ignore_index,
+                               reduction)

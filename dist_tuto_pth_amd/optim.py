@@ -9,6 +9,11 @@ formula (the golden reference for the GPU numerics test).
 
 Update rule (torch SGD semantics, as the reference's optimizer):
     buf = mu * buf + grad ;  p -= lr * buf
+With ``weight_decay`` the gradient is first replaced by
+``g' = grad + weight_decay * p``; with ``nesterov`` the step direction is
+``g' + mu * buf`` instead of ``buf``.  Both are compile-time variants of
+the same kernel.  Dampening is not offered: torch's first-step special
+case for it does not fit buffers that start at zero.
 """
 
 from __future__ import annotations
@@ -45,10 +50,19 @@ def _require_dense_fp32(i, p, grad, buf):
 
 class FusedSGD:
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 0.01,
-                 momentum: float = 0.0, zero_grad_in_step: bool = False):
+                 momentum: float = 0.0, zero_grad_in_step: bool = False,
+                 weight_decay: float = 0.0, nesterov: bool = False):
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no parameters to optimize")
+        if weight_decay < 0.0:
+            raise ValueError(f"FusedSGD: weight_decay must be >= 0, got "
+                             f"{weight_decay}")
+        if nesterov and momentum == 0.0:
+            raise ValueError("FusedSGD: nesterov=True needs a momentum "
+                             "other than 0")
+        self.weight_decay = weight_decay
+        self.nesterov = bool(nesterov)
         self.lr = lr
         self.momentum = momentum
         self.zero_grad_in_step = zero_grad_in_step
@@ -70,18 +84,26 @@ class FusedSGD:
                 ptrs_g.append(p.grad.data_ptr())
                 ptrs_b.append(buf.data_ptr() if buf is not None else 0)
                 numels.append(p.numel())
-            k.sgd_step(ptrs_p, ptrs_g, ptrs_b, numels, self.lr,
-                       self.momentum, self.zero_grad_in_step,
-                       torch.cuda.current_stream().cuda_stream)
+            stream = torch.cuda.current_stream().cuda_stream
+            if self.weight_decay == 0.0 and not self.nesterov:
+                k.sgd_step(ptrs_p, ptrs_g, ptrs_b, numels, self.lr,
+                           self.momentum, self.zero_grad_in_step, stream)
+            else:
+                k.sgd_step(ptrs_p, ptrs_g, ptrs_b, numels, self.lr,
+                           self.momentum, self.zero_grad_in_step, stream,
+                           self.weight_decay, self.nesterov)
             return
         for i, p in enumerate(self.params):
             if p.grad is None:
                 continue
             g = p.grad
+            if self.weight_decay != 0.0:
+                g = g.add(p, alpha=self.weight_decay)
             if self._bufs is not None:
                 buf = self._bufs[i]
                 buf.mul_(self.momentum).add_(g)
-                g = buf
+                g = g.add(buf, alpha=self.momentum) if self.nesterov \
+                    else buf
             p.add_(g, alpha=-self.lr)
             if self.zero_grad_in_step:
                 p.grad.zero_()
