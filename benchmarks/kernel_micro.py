@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel microbenchmark of the fused ConvNet training step
 (hipEvent timing, 1 GPU).  Pinpoints where the step's microseconds go:
-fwd, data-bwd (at each sibling-split), the four weight-gradient tile
+fwd, data-bwd (bundled with gw, and alone: both kernels at each
+sibling-split), the four weight-gradient tile
 segments separately, combine, sgd, prologue.
 
 Run on a GPU box:  python benchmarks/kernel_micro.py [--batch 128]
@@ -95,6 +96,24 @@ def main():
         os.environ["DTP_BWD_SPLIT"] = str(sp)
         results[f"bwd+gw (split={sp})"] = time_fn(bwd)
     os.environ.pop("DTP_BWD_SPLIT", None)
+
+    # the data backward alone, both kernels (DTP_BWD_TILED=0: the
+    # 256-thread strip loop) at each sibling split; "auto" is the default
+    def bwd_data():
+        k.net_bwd_data_raw(pp[2], pp[4], pp[6], tgt.data_ptr(),
+                           ws["one"].data_ptr(), ws.ptrs, B, True, s)
+
+    for tiled in (1, 0):
+        os.environ["DTP_BWD_TILED"] = str(tiled)
+        for sp in ("auto", 1, 2, 4, 8):
+            if sp == "auto":
+                os.environ.pop("DTP_BWD_SPLIT", None)
+            else:
+                os.environ["DTP_BWD_SPLIT"] = str(sp)
+            name = "tiled" if tiled else "strip"
+            results[f"bwd data {name} (split={sp})"] = time_fn(bwd_data)
+    os.environ.pop("DTP_BWD_SPLIT", None)
+    os.environ.pop("DTP_BWD_TILED", None)
     base = 0
     for name, ntiles in k.gw_tiles:  # walk order of the partial kernel
         results[f"gw {name} tiles"] = time_fn(seg(base, ntiles))

@@ -38,7 +38,12 @@ def _needs_build(out, srcs):
     return any(os.path.getmtime(s) > ot for s in srcs)
 
 
-def build(force: bool = False):
+def build(force: bool = False, stage_stamps: bool = False):
+    """Build the extensions.  ``stage_stamps`` builds, instead, the
+    diagnostic ``_kernels_stamps.so`` (net_fused.hip's DTP_STAGE_STAMPS:
+    shader-clock stamps at the stage boundaries of the fused forward and
+    data backward) next to the default ``_kernels.so``, which it leaves
+    alone; only benchmarks/stage_shares.py loads it."""
     os.makedirs(OUT, exist_ok=True)
     inc = sum([["-I", p] for p in _includes()], [])
     common = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -54,6 +59,9 @@ def build(force: bool = False):
                             "cross_entropy.hip"),
          src("common.h", "gemm_bf16.h"), []),
     ]
+    if stage_stamps:
+        targets = [("_kernels_stamps.so", targets[1][1], targets[1][2],
+                    ["-DDTP_STAGE_STAMPS"])]
     for out_name, srcs, hdrs, extra in targets:
         out = os.path.join(OUT, out_name)
         if force or _needs_build(out, srcs + hdrs):
@@ -63,4 +71,5 @@ def build(force: bool = False):
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
+    build(force="--force" in sys.argv,
+          stage_stamps="--stage-stamps" in sys.argv)

@@ -54,6 +54,32 @@ __global__ void step_prologue_kernel(unsigned long long* s, float* loss) {
 #define N_H1 50         // fc1 out
 #define N_CLS 10        // classes
 
+// Stage stamps — DIAGNOSTIC BUILD ONLY (build.py --stage-stamps defines
+// DTP_STAGE_STAMPS; the default build leaves it undefined and every
+// STAGE_STAMP is empty).  Thread 0 of each workgroup stores the shader
+// clock at the stage boundaries of net_fwd_sample / the data backward
+// into a buffer of its own; benchmarks/stage_shares.py turns the
+// differences into per-stage SHARES of a workgroup's time (the stamps
+// perturb the kernels, so lengths are not to be quoted).
+//   bwd: 0 entry, 1 w2 staged + sample start, 2 g_logits, 3 g_h1, 4 g_p2,
+//        5 tile zeroed + scattered, 6 ga2 stashed (head done),
+//        7 conv2-bwd_x partials done, 8 sample done
+//   fwd: 9 entry, 10 x/w staged, 11 conv1+pool1, 12 conv2+pool2,
+//        13 sibling hand-off done, 14 fc1, 15 fc2+softmax (sample done)
+#ifdef DTP_STAGE_STAMPS
+#define STAGE_NSTAMP 16
+#define STAGE_NBLK 4096
+__device__ unsigned long long g_stage_stamps[STAGE_NBLK * STAGE_NSTAMP];
+#define STAGE_STAMP(i)                                                   \
+  do {                                                                   \
+    if (threadIdx.x == 0)                                                \
+      g_stage_stamps[(blockIdx.x % STAGE_NBLK) * STAGE_NSTAMP + (i)] =   \
+          (unsigned long long)clock64();                                 \
+  } while (0)
+#else
+#define STAGE_STAMP(i) do {} while (0)
+#endif
+
 // partial-row access, parameterized on coherence: the in-launch fold
 // variant stores partials sc1 (device-coherent, straight to the
 // coherence point) and reads them back sc1 — ZERO fences, so the
@@ -114,6 +140,7 @@ __device__ __forceinline__ float net_fwd_sample(
     float* p2, float* d3, float* logits) {
   float ret = 0.f;
   {
+    STAGE_STAMP(9);
     // stage input + conv weights
     for (int i = tid; i < 784; i += 256) xs[i] = x[(int64_t)b * 784 + i];
     for (int i = tid; i < N_C1K * 25; i += 256) w1s[i] = w1[i];
@@ -127,6 +154,7 @@ __device__ __forceinline__ float net_fwd_sample(
       if (klo + tid < khi) w2s[N_C2K * 250 + klo + tid] = b2[klo + tid];
     }
     __syncthreads();
+    STAGE_STAMP(10);
 
     // conv1 + pool1 + relu in ONE register-blocked stage: each thread
     // owns a 2x2 pooling window, computes its four conv outputs in
@@ -164,6 +192,7 @@ __device__ __forceinline__ float net_fwd_sample(
       }
     }
     __syncthreads();
+    STAGE_STAMP(11);
 
     // conv2 + dropout2d + pool2 + relu, same register-blocked shape:
     // one thread per pooled cell, four conv outputs in four chains,
@@ -210,6 +239,7 @@ __device__ __forceinline__ float net_fwd_sample(
       m2_ws[(int64_t)b * N_C2K + tid] = rr >= 0x80000000u;
     }
     __syncthreads();
+    STAGE_STAMP(12);
     if (SPLIT && half == 1) {
       // publish: p2 half is sc1-stored (at the coherence point once
       // vmcnt retires) — drain, then write this STEP's token.  A
@@ -282,6 +312,7 @@ __device__ __forceinline__ float net_fwd_sample(
       __syncthreads();
     }
 
+    STAGE_STAMP(13);
     // fc1 (320->50) + relu + dropout: 4 threads per output, shfl reduce
     if (tid < N_H1 * 4) {
       const int n = tid >> 2, q = tid & 3;
@@ -314,6 +345,7 @@ __device__ __forceinline__ float net_fwd_sample(
       }
     }
     __syncthreads();
+    STAGE_STAMP(14);
 
     // fc2 (50->10)
     if (tid < N_CLS) {
@@ -345,6 +377,7 @@ __device__ __forceinline__ float net_fwd_sample(
       ret = lp_t;
     }
     __syncthreads();
+    STAGE_STAMP(15);
   }
   return ret;
 }
@@ -443,6 +476,111 @@ net_fused_fwd_split_kernel(
   }
 }
 
+// The head of one sample's data backward: loss grad -> the zero-padded
+// conv2-out grad tile gd2p[k][16][RS] (plane stride PS; entry
+// (k, oh+4, ow+4) holds the conv2-out grad at [k][oh][ow]) by an
+// NT-thread workgroup.  Every sibling of a sample recomputes it (~35k
+// FMA); sibling 0 also writes glog / gh1 / ga2 for the weight-gradient
+// pass.  Ends on a barrier: the tile is complete for all threads.
+template <int NT, int RS, int PS>
+__device__ __forceinline__ void net_bwd_head(
+    int b, int half, int tid, int training, float sc,
+    const float* __restrict__ wf1, const float* __restrict__ wf2,
+    const int64_t* __restrict__ tgt,
+    const uint8_t* __restrict__ m2_ws,
+    const uint8_t* __restrict__ idx2_ws,
+    const float* __restrict__ h1_ws,
+    const uint8_t* __restrict__ m3_ws,
+    const float* __restrict__ logp_ws,
+    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
+    float* __restrict__ ga2_ws,
+    // LDS carve (sizes: 10, 50, 50, 320, 20 * PS)
+    float* glg, float* gd3, float* gh1, float* gp2, float* gd2p) {
+  {
+    // g_logits = (exp(logp) - onehot) * gl / B
+    __syncthreads();
+    STAGE_STAMP(1);
+    if (tid < N_CLS) {
+      const float lp = logp_ws[(int64_t)b * N_CLS + tid];
+      const float g = (__expf(lp) -
+                       (tid == (int)tgt[b] ? 1.f : 0.f)) * sc;
+      glg[tid] = g;
+      if (half == 0)
+        glog_ws[(int64_t)b * N_CLS + tid] = g;
+    }
+    __syncthreads();
+    STAGE_STAMP(2);
+
+    // g_d3 = wf2^T g_logits ; through dropout + relu -> g_h1pre
+    if (tid < N_H1) {
+      float acc = 0.f;
+      #pragma unroll
+      for (int n = 0; n < N_CLS; ++n)
+        acc += wf2[n * N_H1 + tid] * glg[n];
+      gd3[tid] = acc;
+      float g = acc;
+      if (training) {
+        g = m3_ws[(int64_t)b * N_H1 + tid] ? g * 2.f : 0.f;
+      }
+      if (h1_ws[(int64_t)b * N_H1 + tid] <= 0.f) g = 0.f;
+      gh1[tid] = g;
+      if (half == 0)
+        gh1_ws[(int64_t)b * N_H1 + tid] = g;
+    }
+    __syncthreads();
+    STAGE_STAMP(3);
+
+    // g_p2 = wf1^T g_h1pre  (320 outputs x 50), four accumulator
+    // chains over the reduction dim (wf1 rows are coalesced global
+    // reads; the single 50-deep load+FMA chain was latency-bound)
+    for (int i = tid; i < N_P2; i += NT) {
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      #pragma unroll
+      for (int n = 0; n < 48; n += 4) {
+        a0 += wf1[n * N_P2 + i] * gh1[n];
+        a1 += wf1[(n + 1) * N_P2 + i] * gh1[n + 1];
+        a2 += wf1[(n + 2) * N_P2 + i] * gh1[n + 2];
+        a3 += wf1[(n + 3) * N_P2 + i] * gh1[n + 3];
+      }
+      a0 += wf1[48 * N_P2 + i] * gh1[48];
+      a1 += wf1[49 * N_P2 + i] * gh1[49];
+      gp2[i] = (a0 + a1) + (a2 + a3);
+    }
+    __syncthreads();
+    STAGE_STAMP(4);
+
+    // pool2 bwd + dropout2d bwd -> g_a2, scattered STRAIGHT into the
+    // padded gd2p tile with dropout applied (r2: the old path staged
+    // through a dense gd2 buffer — zero + scatter + full re-read, an
+    // extra 2.5k LDS ops per sample for nothing; gd2 is gone)
+    for (int i = tid; i < N_C2K * PS; i += NT) gd2p[i] = 0.f;
+    __syncthreads();
+    for (int i = tid; i < N_P2; i += NT) {
+      const int c = i / 16, oh = (i / 4) % 4, ow = i % 4;
+      const uint8_t v = idx2_ws[(int64_t)b * N_P2 + i];
+      if (!(v & 4)) {
+        const int am = v & 3;
+        const int fr = oh * 2 + (am >> 1), fc = ow * 2 + (am & 1);
+        float g = gp2[i];
+        if (training)
+          g = m2_ws[(int64_t)b * N_C2K + c] ? g * 2.f : 0.f;
+        gd2p[c * PS + (fr + 4) * RS + (fc + 4)] = g;
+      }
+    }
+    __syncthreads();
+    STAGE_STAMP(5);
+    if (half == 0) {  // stash the dense conv2-out grad for the gw pass
+      for (int i = tid; i < N_A2; i += NT) {
+        const int k = i / 64, oh = (i / 8) % 8, ow = i % 8;
+        ga2_ws[(int64_t)b * N_A2 + i] =
+            gd2p[k * PS + (oh + 4) * RS + (ow + 4)];
+      }
+    }
+    __syncthreads();
+    STAGE_STAMP(6);
+  }
+}
+
 // One (sample, sibling-half)'s data backward: loss grad -> g_a1 (conv1
 // output grad).  `split` sibling workgroups cooperate on each sample:
 // the cheap early stages (g_logits .. gd2p staging, ~35k FMA) are
@@ -465,83 +603,10 @@ __device__ __forceinline__ void net_bwd_sample(
     // LDS carve (sizes: 5000, 10, 50, 50, 320, 6080)
     const float* w2s, float* glg, float* gd3, float* gh1, float* gp2,
     float* gd2p) {
+  net_bwd_head<256, 19, 304>(b, half, tid, training, sc, wf1, wf2, tgt,
+                             m2_ws, idx2_ws, h1_ws, m3_ws, logp_ws, glog_ws,
+                             gh1_ws, ga2_ws, glg, gd3, gh1, gp2, gd2p);
   {
-    // g_logits = (exp(logp) - onehot) * gl / B
-    __syncthreads();
-    if (tid < N_CLS) {
-      const float lp = logp_ws[(int64_t)b * N_CLS + tid];
-      const float g = (__expf(lp) -
-                       (tid == (int)tgt[b] ? 1.f : 0.f)) * sc;
-      glg[tid] = g;
-      if (half == 0)
-        glog_ws[(int64_t)b * N_CLS + tid] = g;
-    }
-    __syncthreads();
-
-    // g_d3 = wf2^T g_logits ; through dropout + relu -> g_h1pre
-    if (tid < N_H1) {
-      float acc = 0.f;
-      #pragma unroll
-      for (int n = 0; n < N_CLS; ++n)
-        acc += wf2[n * N_H1 + tid] * glg[n];
-      gd3[tid] = acc;
-      float g = acc;
-      if (training) {
-        g = m3_ws[(int64_t)b * N_H1 + tid] ? g * 2.f : 0.f;
-      }
-      if (h1_ws[(int64_t)b * N_H1 + tid] <= 0.f) g = 0.f;
-      gh1[tid] = g;
-      if (half == 0)
-        gh1_ws[(int64_t)b * N_H1 + tid] = g;
-    }
-    __syncthreads();
-
-    // g_p2 = wf1^T g_h1pre  (320 outputs x 50), four accumulator
-    // chains over the reduction dim (wf1 rows are coalesced global
-    // reads; the single 50-deep load+FMA chain was latency-bound)
-    for (int i = tid; i < N_P2; i += 256) {
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-      #pragma unroll
-      for (int n = 0; n < 48; n += 4) {
-        a0 += wf1[n * N_P2 + i] * gh1[n];
-        a1 += wf1[(n + 1) * N_P2 + i] * gh1[n + 1];
-        a2 += wf1[(n + 2) * N_P2 + i] * gh1[n + 2];
-        a3 += wf1[(n + 3) * N_P2 + i] * gh1[n + 3];
-      }
-      a0 += wf1[48 * N_P2 + i] * gh1[48];
-      a1 += wf1[49 * N_P2 + i] * gh1[49];
-      gp2[i] = (a0 + a1) + (a2 + a3);
-    }
-    __syncthreads();
-
-    // pool2 bwd + dropout2d bwd -> g_a2, scattered STRAIGHT into the
-    // padded gd2p tile with dropout applied (r2: the old path staged
-    // through a dense gd2 buffer — zero + scatter + full re-read, an
-    // extra 2.5k LDS ops per sample for nothing; gd2 is gone)
-    for (int i = tid; i < N_C2K * 304; i += 256) gd2p[i] = 0.f;
-    __syncthreads();
-    for (int i = tid; i < N_P2; i += 256) {
-      const int c = i / 16, oh = (i / 4) % 4, ow = i % 4;
-      const uint8_t v = idx2_ws[(int64_t)b * N_P2 + i];
-      if (!(v & 4)) {
-        const int am = v & 3;
-        const int fr = oh * 2 + (am >> 1), fc = ow * 2 + (am & 1);
-        float g = gp2[i];
-        if (training)
-          g = m2_ws[(int64_t)b * N_C2K + c] ? g * 2.f : 0.f;
-        gd2p[c * 304 + (fr + 4) * 19 + (fc + 4)] = g;
-      }
-    }
-    __syncthreads();
-    if (half == 0) {  // stash the dense conv2-out grad for the gw pass
-      for (int i = tid; i < N_A2; i += 256) {
-        const int k = i / 64, oh = (i / 8) % 8, ow = i % 8;
-        ga2_ws[(int64_t)b * N_A2 + i] =
-            gd2p[k * 304 + (oh + 4) * 19 + (ow + 4)];
-      }
-    }
-    __syncthreads();
-
     // conv2 bwd_x through the padded tile + pool1 bwd, register-blocked
     // 4-wide: each thread owns FOUR horizontally-adjacent pooled
     // positions (one accumulator chain each); a (k, r) row contributes
@@ -592,6 +657,7 @@ __device__ __forceinline__ void net_bwd_sample(
       }
     }
     __syncthreads();
+    STAGE_STAMP(8);
   }
 }
 
@@ -631,6 +697,7 @@ net_fused_bwd_kernel(
   __shared__ float gd2p[N_C2K * 304];
   const int tid = threadIdx.x;
 
+  STAGE_STAMP(0);
   for (int i = tid; i < N_C2K * 250; i += 256) w2s[i] = w2[i];
   const float sc = gl[0] / B;
 
@@ -639,6 +706,199 @@ net_fused_bwd_kernel(
                    wf1, wf2, tgt, idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws,
                    logp_ws, glog_ws, gh1_ws, ga2_ws, ga1_ws,
                    w2s, glg, gd3, gh1, gp2, gd2p);
+  }
+}
+
+// The data backward with the conv2-bwd_x loop re-blocked for 16-byte LDS
+// reads and full SIMDs (512 threads = 2 waves per SIMD).  Same head as
+// net_fused_bwd_kernel; the hot loop differs:
+//  - a work item is a 2-row x 4-wide tile of pooled positions (pos =
+//    hp*3 + wq, 18 per channel) of one input channel c, over ONE group
+//    of 4 of conv2's 20 output channels k.  Per k it reads 6 rows x 8
+//    floats of the padded tile and the 25-float filter — 12 + 7
+//    ds_read_b128 — and feeds 200 FMAs; the five k-group partials of a
+//    tile are summed through LDS in fixed order (no atomics:
+//    deterministic, and the value does not depend on `split`).
+//  - tile row stride 20, plane stride 332: a row segment is two aligned
+//    float4.  Brute-force scan over the item -> lane map below against
+//    the ds_read_b128 lane groups (4 x 16 lanes, 16 bank quads): with
+//    the channel as the fastest lane index, (20, 332) is conflict-free
+//    (4 LDS cycles per read) for 90-tile rounds of 5 or 10 channels;
+//    plane strides 320/324/328 cost 4.25-4.75, row stride 16 5.0-6.0,
+//    and a position-fastest lane order 7.75 or more at any stride.
+//  - w2 is staged as [k][c_local][28]: each (k, c) filter 16-byte
+//    aligned, and only this sibling's input channels (half of w2 at
+//    split >= 2).  Lanes of equal c read one address (broadcast).
+//  - siblings partition (channel half) x (position range): split = 1
+//    owns everything, 2 a channel half, 4 and 8 cut each half's 18
+//    positions into 2 and 4 ranges.  A round is <= 90 tiles x 5 k-groups
+//    = 450 of 512 lanes (88%).
+#define BT_NT 512   // threads
+#define BT_RS 20    // tile row stride (floats)
+#define BT_PS 332   // tile plane stride
+#define BT_WS 28    // staged filter stride
+#define BT_KG 5     // k groups (of N_C2K / BT_KG = 4 channels)
+#define BT_ROUND 90 // tiles per round: BT_ROUND * BT_KG <= BT_NT
+static_assert(BT_ROUND * BT_KG <= BT_NT, "one item per thread per round");
+static_assert(BT_RS % 4 == 0 && BT_PS % 4 == 0 && BT_WS % 4 == 0 &&
+              BT_PS >= 16 * BT_RS && BT_WS >= 25, "aligned float4 reads");
+
+__global__ void
+__launch_bounds__(BT_NT)
+net_fused_bwd_tiled_kernel(
+    const float* __restrict__ w2, const float* __restrict__ wf1,
+    const float* __restrict__ wf2,
+    const int64_t* __restrict__ tgt,
+    const float* __restrict__ gl,      // dLoss (device scalar)
+    const uint8_t* __restrict__ idx1_ws,
+    const uint8_t* __restrict__ m2_ws,
+    const uint8_t* __restrict__ idx2_ws,
+    const float* __restrict__ h1_ws,
+    const uint8_t* __restrict__ m3_ws,
+    const float* __restrict__ logp_ws,
+    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
+    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,
+    int B, int training, int split) {
+  __shared__ __attribute__((aligned(16))) float w2p[N_C2K * N_C1K * BT_WS];
+  __shared__ __attribute__((aligned(16))) float gd2p[N_C2K * BT_PS];
+  __shared__ __attribute__((aligned(16))) float part[BT_ROUND * BT_KG * 8];
+  __shared__ float glg[N_CLS];
+  __shared__ float gd3[N_H1];
+  __shared__ float gh1[N_H1];
+  __shared__ float gp2[N_P2];
+  const int tid = threadIdx.x;
+
+  // the grid is B * split or a multiple of 8 (host), so a workgroup
+  // keeps one sibling index over its grid-stride loop
+  const int half = blockIdx.x % split;
+  const int cgs = split >= 2 ? 2 : 1, prs = split / cgs;
+  const int nc = N_C1K / cgs, c0 = (half / prs) * nc;
+  const int p0 = 18 * (half % prs) / prs;
+  const int p1 = 18 * (half % prs + 1) / prs;
+  const int ppr = BT_ROUND / nc;  // positions per round
+
+  STAGE_STAMP(0);
+  for (int i = tid; i < N_C2K * nc * 25; i += BT_NT) {
+    const int kc = i / 25, j = i - kc * 25;
+    const int k = kc / nc, cl = kc - k * nc;
+    w2p[kc * BT_WS + j] = w2[(k * N_C1K + c0 + cl) * 25 + j];
+  }
+  const float sc = gl[0] / B;
+
+  for (int bb = blockIdx.x; bb < B * split; bb += gridDim.x) {
+    const int b = bb / split;
+    // (its leading barrier also orders the w2p staging and the previous
+    // sample's last tile reads)
+    // opaque per sample: with one g_p2 output per lane the 50 wf1
+    // loads are loop-invariant, and hoisted out of this loop they
+    // spilled 105 registers to scratch
+    const float* wf1_b = wf1;
+    asm volatile("" : "+s"(wf1_b));
+    net_bwd_head<BT_NT, BT_RS, BT_PS>(
+        b, half, tid, training, sc, wf1_b, wf2, tgt, m2_ws, idx2_ws, h1_ws,
+        m3_ws, logp_ws, glog_ws, gh1_ws, ga2_ws, glg, gd3, gh1, gp2, gd2p);
+
+    for (int pb = p0; pb < p1; pb += ppr) {
+      const int nt = min(ppr, p1 - pb) * nc;  // tiles this round
+      if (tid < nt * BT_KG) {
+        const int kg = tid / nt, tl = tid - kg * nt;
+        const int pl = tl / nc, cl = tl - pl * nc;
+        const int pos = pb + pl, hp = pos / 3, wc0 = (pos % 3) * 4;
+        // rows 2hp .. 2hp+5 of the padded tile cover both output rows'
+        // five filter rows; columns wc0 .. wc0+7 all four outputs' taps
+        const float4* gk = reinterpret_cast<const float4*>(
+            gd2p + kg * (N_C2K / BT_KG) * BT_PS + 2 * hp * BT_RS + wc0);
+        const float4* wk = reinterpret_cast<const float4*>(
+            w2p + (kg * (N_C2K / BT_KG) * nc + cl) * BT_WS);
+        const int wstep = nc * (BT_WS / 4);
+        float q[8];
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = 0.f;
+        // two register sets in ping-pong: the other set's reads (next k)
+        // are issued ahead of this set's arithmetic.  The pair loop is
+        // NOT unrolled: fully unrolled, the scheduler hoisted all four
+        // k's reads (4 x 76 registers) and spilled to scratch.
+        float4 ea[12], wa[7], eb[12], wb[7];
+        auto load = [&](float4* e, float4* w, int kk) {
+          const float4* gn = gk + kk * (BT_PS / 4);
+          const float4* wn = wk + kk * wstep;
+          #pragma unroll
+          for (int j = 0; j < 6; ++j) {
+            e[2 * j] = gn[j * (BT_RS / 4)];
+            e[2 * j + 1] = gn[j * (BT_RS / 4) + 1];
+          }
+          #pragma unroll
+          for (int j = 0; j < 7; ++j) w[j] = wn[j];
+        };
+        // out(h, w) += g[k][h - r][w - s] * w2[k][c][r][s]; tile entry
+        // (oh + 4, ow + 4) -> local row a - r + 4, local col jj + 4 - s
+        auto fma200 = [&](const float4* e, const float4* w) {
+          float ev[6][8], wv[28];
+          #pragma unroll
+          for (int j = 0; j < 12; ++j) {
+            ev[j >> 1][(j & 1) * 4 + 0] = e[j].x;
+            ev[j >> 1][(j & 1) * 4 + 1] = e[j].y;
+            ev[j >> 1][(j & 1) * 4 + 2] = e[j].z;
+            ev[j >> 1][(j & 1) * 4 + 3] = e[j].w;
+          }
+          #pragma unroll
+          for (int j = 0; j < 7; ++j) {
+            wv[4 * j] = w[j].x; wv[4 * j + 1] = w[j].y;
+            wv[4 * j + 2] = w[j].z; wv[4 * j + 3] = w[j].w;
+          }
+          #pragma unroll
+          for (int r = 0; r < 5; ++r) {
+            #pragma unroll
+            for (int s = 0; s < 5; ++s) {
+              #pragma unroll
+              for (int a = 0; a < 2; ++a) {
+                #pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+                  q[a * 4 + jj] = fmaf(ev[a - r + 4][jj + 4 - s],
+                                       wv[r * 5 + s], q[a * 4 + jj]);
+              }
+            }
+          }
+        };
+        static_assert((N_C2K / BT_KG) % 2 == 0, "k pairs");
+        load(ea, wa, 0);
+        #pragma unroll 1
+        for (int kk = 0; kk < N_C2K / BT_KG; kk += 2) {
+          load(eb, wb, kk + 1);
+          fma200(ea, wa);
+          // (the last pair re-reads its own second k: in bounds, unused)
+          load(ea, wa, min(kk + 2, N_C2K / BT_KG - 1));
+          fma200(eb, wb);
+        }
+        float4* pp = reinterpret_cast<float4*>(part + tid * 8);
+        pp[0] = make_float4(q[0], q[1], q[2], q[3]);
+        pp[1] = make_float4(q[4], q[5], q[6], q[7]);
+      }
+      __syncthreads();
+      STAGE_STAMP(7);
+      // fixed-order sum of the k-group partials, then pool1 bwd: each
+      // pooled position owns its 2x2 ga1 window, all four slots written
+      for (int o = tid; o < nt * 8; o += BT_NT) {
+        const int tl = o >> 3, j = o & 7;
+        float g = part[o];
+        #pragma unroll
+        for (int kg = 1; kg < BT_KG; ++kg) g += part[kg * nt * 8 + o];
+        const int pl = tl / nc, c = c0 + tl - pl * nc;
+        const int pos = pb + pl;
+        const int h = (pos / 3) * 2 + (j >> 2), wc = (pos % 3) * 4 + (j & 3);
+        const uint8_t v = idx1_ws[(int64_t)b * N_P1 + c * 144 + h * 12 + wc];
+        const int am = v & 3;
+        if (v & 4) g = 0.f;
+        float* gp = ga1_ws + (int64_t)b * N_A1 + c * 576 + h * 2 * 24 +
+                    wc * 2;
+        *reinterpret_cast<float2*>(gp) =
+            make_float2(am == 0 ? g : 0.f, am == 1 ? g : 0.f);
+        *reinterpret_cast<float2*>(gp + 24) =
+            make_float2(am == 2 ? g : 0.f, am == 3 ? g : 0.f);
+      }
+      __syncthreads();
+    }
+    STAGE_STAMP(8);
   }
 }
 
@@ -1668,8 +1928,9 @@ void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
 }
 
 // sibling workgroups per sample of the data backward: enough to fill
-// the 256 CUs (with the 4-wide-blocked hot loop, split=2 at B=128 —
-// 256 workgroups, 180 strips each — is fastest, profiles/).
+// the 256 CUs (split=2 at B=128 — 256 workgroups, one channel half
+// each — is fastest with the tiled kernel as it was with the strip
+// loop; re-swept at B=64/128/4096, profiles/).
 // DTP_BWD_SPLIT=1/2/4/8 overrides; read on every call, the
 // microbenchmark changes it between timings.
 static int bwd_split(int B) {
@@ -1682,12 +1943,23 @@ static int bwd_split(int B) {
   return split;
 }
 
+// which data-backward kernel: the re-blocked 512-thread one (default)
+// or, with DTP_BWD_TILED=0, the 256-thread strip loop that the fwdbwd
+// and single-launch kernels still share.  Read on every call, like
+// DTP_BWD_SPLIT.
+static bool bwd_tiled() {
+  const char* e = std::getenv("DTP_BWD_TILED");
+  return !(e && std::atoi(e) == 0);
+}
+
 static void launch_bwd_data(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
                             uintptr_t tgt, uintptr_t gl, const NetWs& w,
                             int B, bool training, hipStream_t s) {
   const int split = bwd_split(B);
-  hipLaunchKernelGGL(net_fused_bwd_kernel,
-                     dim3(grid_for((int64_t)B * split, 1)), dim3(256), 0, s,
+  auto* kern = bwd_tiled() ? net_fused_bwd_tiled_kernel
+                           : net_fused_bwd_kernel;
+  hipLaunchKernelGGL(kern, dim3(grid_for((int64_t)B * split, 1)),
+                     dim3(bwd_tiled() ? BT_NT : 256), 0, s,
                      (const float*)w2, (const float*)wf1, (const float*)wf2,
                      (const int64_t*)tgt, (const float*)gl,
                      (const uint8_t*)w.idx1, (const uint8_t*)w.m2,
@@ -1759,6 +2031,35 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
             use_loss_part ? w.loss : nullptr, fwd_grid(B),
             seed_bump(training, seed_dev), S(stream));
 }
+
+// raw data-backward launch (microbenchmarks: net_fused_bwd bundles it
+// with the weight-gradient kernels)
+void net_bwd_data_raw(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
+                      uintptr_t tgt, uintptr_t gl,
+                      const std::vector<uintptr_t>& ws_v, int B,
+                      bool training, uintptr_t stream) {
+  if (B < 1) throw std::invalid_argument("net_bwd_data_raw: B must be >= 1");
+  launch_bwd_data(w2, wf1, wf2, tgt, gl, net_ws(ws_v), B, training,
+                  S(stream));
+}
+
+#ifdef DTP_STAGE_STAMPS
+// diagnostic build only: zero / read back the stage-stamp buffer as
+// [STAGE_NBLK][STAGE_NSTAMP] (synchronizes the device)
+void stage_stamps_clear() {
+  static const std::vector<unsigned long long> z(STAGE_NBLK * STAGE_NSTAMP);
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stage_stamps), z.data(),
+                              z.size() * sizeof(unsigned long long)));
+}
+std::vector<unsigned long long> stage_stamps() {
+  std::vector<unsigned long long> v(STAGE_NBLK * STAGE_NSTAMP);
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpyFromSymbol(v.data(), HIP_SYMBOL(g_stage_stamps),
+                                v.size() * sizeof(unsigned long long)));
+  return v;
+}
+#endif
 
 // Combined fwd+bwd (one dispatch) + weight gradients: a 3-dispatch
 // training step (vs 4 for fwd / bwd / partial / combine).  wts_v are
@@ -1935,6 +2236,12 @@ void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
 void register_net_fused(pybind11::module_& m) {
   m.def("net_fused_fwd", &net_fused_fwd);
   m.def("net_fused_bwd", &net_fused_bwd);
+  m.def("net_bwd_data_raw", &net_bwd_data_raw);
+#ifdef DTP_STAGE_STAMPS
+  m.def("stage_stamps", &stage_stamps);
+  m.def("stage_stamps_clear", &stage_stamps_clear);
+  m.attr("STAGE_NSTAMP") = STAGE_NSTAMP;
+#endif
   m.def("net_fused_fwdbwd", &net_fused_fwdbwd);
   m.def("net_step", &net_step);
   m.def("net_step_available", &net_step_available);

@@ -4,7 +4,8 @@ Four dispatches per training step instead of ~30 per-op launches:
 one kernel for the entire forward (conv1..log_softmax+NLL,
 train_dist.py:64-71 + :120, conv+pool register-fused, per-block loss
 partials), one for the data backward (sibling-workgroup split,
-4-wide register-blocked transposed conv), one segmented partial
+2x4-tile register-blocked transposed conv with the conv2 channels split
+over lanes), one segmented partial
 weight-gradient kernel ([conv2 x8 | conv1 x8 | fc1 | fc2] tiles x batch
 chunks), and one combine kernel that also finalizes the loss, advances
 the dropout seed, and (single-GPU) applies the SGD+momentum update.
