@@ -37,6 +37,9 @@
 // accesses of V elements.  The eight accumulators are added as a fixed
 // tree, the 64 lanes by wave shuffles, the 4 waves through LDS.
 //
+// The access (load_vec / store_vec), the two sums (tree8, block_sum) and
+// the dispatch on dtype and width (by_dtype_width) are common.h's.
+//
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_batchnorm().
 
@@ -50,51 +53,6 @@
 namespace {
 
 constexpr int GROUP = 8;  // elements per accumulation group
-constexpr int NWAVE = BLK / 64;
-
-// one access of BYTES bytes
-template <int BYTES> struct Raw;
-template <> struct Raw<2> { using type = uint16_t; };
-template <> struct Raw<4> { using type = uint32_t; };
-template <> struct Raw<8> { using type = uint2; };
-template <> struct Raw<16> { using type = uint4; };
-
-template <typename T, int V>
-union Vec {
-  typename Raw<sizeof(T) * V>::type raw;
-  T e[V];
-};
-
-template <typename T, int V>
-__device__ __forceinline__ void load_vec(const T* p, float (&f)[V]) {
-  Vec<T, V> u;
-  u.raw = *reinterpret_cast<const typename Raw<sizeof(T) * V>::type*>(p);
-#pragma unroll
-  for (int j = 0; j < V; ++j) f[j] = to_f(u.e[j]);
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void store_vec(T* p, const float (&f)[V]) {
-  Vec<T, V> u;
-#pragma unroll
-  for (int j = 0; j < V; ++j) from_f(f[j], u.e[j]);
-  *reinterpret_cast<typename Raw<sizeof(T) * V>::type*>(p) = u.raw;
-}
-
-// sum over the block in a fixed order; every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // sh may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-static_assert(NWAVE == 4, "block_sum adds four waves");
-
-__device__ __forceinline__ float tree8(const float (&a)[GROUP]) {
-  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-}
 
 // The slice of block (c, s) = (blockIdx.x, blockIdx.y): nb planes of HW
 // elements, plane p at first + p*pstride.
@@ -387,75 +345,6 @@ int pick_v(int elem_bytes, int64_t HW, std::initializer_list<uintptr_t> ptrs) {
   return 1;
 }
 
-struct FwdArgs {
-  uintptr_t x, res, y, mean, stat, gamma, beta, ws;
-  int B, C, HW, P, S, eval, relu;
-  float eps;
-};
-
-template <typename T, int V>
-void launch_stats(const FwdArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((bn_stats_kernel<T, V>), dim3(a.C, a.S), dim3(BLK), 0, st,
-                     (const T*)a.x, (float*)a.ws, a.B, a.C, a.HW, a.P);
-}
-
-template <typename T, int V>
-void launch_apply(const FwdArgs& a, hipStream_t st) {
-  const uint32_t hwv = a.HW / V;
-  const uint32_t nvec = (uint32_t)a.B * a.C * hwv;
-  hipLaunchKernelGGL((bn_apply_kernel<T, V>), dim3(grid_for(nvec, BLK)),
-                     dim3(BLK), 0, st, (const T*)a.x, (const T*)a.res, (T*)a.y,
-                     (const float*)a.mean, (const float*)a.stat,
-                     (const float*)a.gamma, (const float*)a.beta, a.eps,
-                     a.eval, a.relu, nvec, hwv, (uint32_t)a.C);
-}
-
-struct BwdArgs {
-  uintptr_t x, gy, y, mean, stat, gamma, dgamma, dbeta, gx, gres, ws;
-  int B, C, HW, P, S, eval;
-  float eps;
-};
-
-template <typename T, int V>
-void launch_bwd_reduce(const BwdArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, V>), dim3(a.C, a.S), dim3(BLK),
-                     0, st, (const T*)a.x, (const T*)a.gy, (const T*)a.y,
-                     (const float*)a.mean, (const float*)a.stat, a.eps,
-                     a.eval, (float*)a.ws, a.B, a.C, a.HW, a.P);
-}
-
-template <typename T, int V>
-void launch_bwd_apply(const BwdArgs& a, hipStream_t st) {
-  const uint32_t hwv = a.HW / V;
-  const uint32_t nvec = (uint32_t)a.B * a.C * hwv;
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V>), dim3(grid_for(nvec, BLK)),
-                     dim3(BLK), 0, st, (const T*)a.x, (const T*)a.gy,
-                     (const T*)a.y, (const float*)a.mean,
-                     (const float*)a.stat, (const float*)a.gamma,
-                     (const float*)a.dgamma, (const float*)a.dbeta, (T*)a.gx,
-                     (T*)a.gres, a.eps, a.eval, (float)a.B * (float)a.HW,
-                     nvec, hwv, (uint32_t)a.C);
-}
-
-// call LAUNCH<T, V>(args, stream) for the runtime dtype and width
-#define BN_DISPATCH(LAUNCH, is_bf16, v, args, st)                            \
-  do {                                                                       \
-    if (is_bf16) {                                                           \
-      switch (v) {                                                           \
-        case 8: LAUNCH<bf16_t, 8>(args, st); break;                          \
-        case 4: LAUNCH<bf16_t, 4>(args, st); break;                          \
-        case 2: LAUNCH<bf16_t, 2>(args, st); break;                          \
-        default: LAUNCH<bf16_t, 1>(args, st); break;                         \
-      }                                                                      \
-    } else {                                                                 \
-      switch (v) {                                                           \
-        case 4: LAUNCH<float, 4>(args, st); break;                           \
-        case 2: LAUNCH<float, 2>(args, st); break;                           \
-        default: LAUNCH<float, 1>(args, st); break;                          \
-      }                                                                      \
-    }                                                                        \
-  } while (0)
-
 int planes_per_slice(int64_t B, int64_t C, int64_t HW, int S) {
   if (S != batchnorm2d_splits(B, C, HW))
     throw std::invalid_argument(
@@ -486,29 +375,32 @@ void batchnorm2d_fwd(uintptr_t x, uintptr_t res, uintptr_t y, uintptr_t gamma,
     throw std::invalid_argument(
         "batchnorm2d: running_mean and running_var come together");
   const int es = is_bf16 ? 2 : 4;
-  FwdArgs a;
-  a.x = x; a.res = res; a.y = y; a.gamma = gamma; a.beta = beta; a.ws = ws;
-  a.B = (int)B; a.C = (int)C; a.HW = (int)HW;
-  a.eval = !training; a.relu = relu; a.eps = (float)eps;
-  a.S = 1; a.P = (int)B;
   if (training) {
-    a.S = splits;
-    a.P = planes_per_slice(B, C, HW, splits);
-    const int vs = pick_v(es, HW, {x});
-    BN_DISPATCH(launch_stats, is_bf16, vs, a, S(stream));
+    const int P = planes_per_slice(B, C, HW, splits);
+    by_dtype_width(is_bf16, pick_v(es, HW, {x}), [&](auto* t, auto v) {
+      using T = elem_t<decltype(t)>;
+      hipLaunchKernelGGL((bn_stats_kernel<T, v()>), dim3(C, splits), dim3(BLK),
+                         0, S(stream), (const T*)x, (float*)ws, (int)B, (int)C,
+                         (int)HW, P);
+    });
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0,
                        S(stream), (const float*)ws, (int)C, splits,
                        (float)eps, (float)momentum, (float*)save_mean,
                        (float*)save_invstd, (float*)run_mean,
                        (float*)run_var);
-    a.mean = save_mean;
-    a.stat = save_invstd;
-  } else {
-    a.mean = run_mean;
-    a.stat = run_var;
   }
-  const int va = pick_v(es, HW, {x, res, y});
-  BN_DISPATCH(launch_apply, is_bf16, va, a, S(stream));
+  const uintptr_t mean = training ? save_mean : run_mean;
+  const uintptr_t stat = training ? save_invstd : run_var;
+  by_dtype_width(is_bf16, pick_v(es, HW, {x, res, y}), [&](auto* t, auto v) {
+    using T = elem_t<decltype(t)>;
+    const uint32_t hwv = (uint32_t)HW / v();
+    const uint32_t nvec = (uint32_t)B * (uint32_t)C * hwv;
+    hipLaunchKernelGGL((bn_apply_kernel<T, v()>), dim3(grid_for(nvec, BLK)),
+                       dim3(BLK), 0, S(stream), (const T*)x, (const T*)res,
+                       (T*)y, (const float*)mean, (const float*)stat,
+                       (const float*)gamma, (const float*)beta, (float)eps,
+                       (int)!training, (int)relu, nvec, hwv, (uint32_t)C);
+  });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -526,22 +418,32 @@ void batchnorm2d_bwd(uintptr_t x, uintptr_t gy, uintptr_t y, uintptr_t gamma,
   if (!x || !gy || !mean || !stat || !gamma || !dgamma || !dbeta || !ws)
     throw std::invalid_argument("batchnorm2d_bwd: null tensor");
   const int es = is_bf16 ? 2 : 4;
-  BwdArgs a;
-  a.x = x; a.gy = gy; a.y = y; a.mean = mean; a.stat = stat; a.gamma = gamma;
-  a.dgamma = dgamma; a.dbeta = dbeta; a.gx = gx; a.gres = gres; a.ws = ws;
-  a.B = (int)B; a.C = (int)C; a.HW = (int)HW;
-  a.eval = !training; a.eps = (float)eps;
-  a.S = splits;
-  a.P = planes_per_slice(B, C, HW, splits);
-  const int vr = pick_v(es, HW, {x, gy, y});
-  BN_DISPATCH(launch_bwd_reduce, is_bf16, vr, a, S(stream));
+  const int P = planes_per_slice(B, C, HW, splits);
+  const int eval = !training;
+  by_dtype_width(is_bf16, pick_v(es, HW, {x, gy, y}), [&](auto* t, auto v) {
+    using T = elem_t<decltype(t)>;
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, v()>), dim3(C, splits),
+                       dim3(BLK), 0, S(stream), (const T*)x, (const T*)gy,
+                       (const T*)y, (const float*)mean, (const float*)stat,
+                       (float)eps, eval, (float*)ws, (int)B, (int)C, (int)HW,
+                       P);
+  });
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0,
                      S(stream), (const float*)ws, (int)C, splits,
                      (float*)dgamma, (float*)dbeta);
-  if (gx || gres) {
-    const int va = pick_v(es, HW, {x, gy, y, gx, gres});
-    BN_DISPATCH(launch_bwd_apply, is_bf16, va, a, S(stream));
-  }
+  if (gx || gres)
+    by_dtype_width(
+        is_bf16, pick_v(es, HW, {x, gy, y, gx, gres}), [&](auto* t, auto v) {
+          using T = elem_t<decltype(t)>;
+          const uint32_t hwv = (uint32_t)HW / v();
+          const uint32_t nvec = (uint32_t)B * (uint32_t)C * hwv;
+          hipLaunchKernelGGL(
+              (bn_bwd_apply_kernel<T, v()>), dim3(grid_for(nvec, BLK)),
+              dim3(BLK), 0, S(stream), (const T*)x, (const T*)gy, (const T*)y,
+              (const float*)mean, (const float*)stat, (const float*)gamma,
+              (const float*)dgamma, (const float*)dbeta, (T*)gx, (T*)gres,
+              (float)eps, eval, (float)B * (float)HW, nvec, hwv, (uint32_t)C);
+        });
   HIP_CHECK(hipGetLastError());
 }
 

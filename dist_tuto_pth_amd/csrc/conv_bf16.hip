@@ -28,6 +28,9 @@
 // gw_combine_kernel sums in split order: no float atomics, bitwise
 // reproducible.  gb is the column-sum of the gy tile and rides along.
 //
+// A chunk (gemm_bf16.h's Chunk) and the epilogue's 8 converted outputs
+// (store8) are common.h's Vec: 8 elements that move as one aligned value.
+//
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_conv_bf16().
 
@@ -122,7 +125,7 @@ __device__ __forceinline__ Chunk conv_gather8(const ConvSrc& g, int kk,
     if (sx0 >= 0 && sx0 + 8 <= g.Ws) {
       const int64_t idx = row + sx0;
       if (g.vec && (idx & 7) == 0) {
-        c.v = *reinterpret_cast<const uint4*>(g.p + idx);
+        c.raw = *reinterpret_cast<const uint4*>(g.p + idx);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) c.e[j] = g.p[idx + j];
@@ -235,7 +238,7 @@ struct GyRowsLoader {
         if (pix + 8 <= OHW && q + 8 <= kend) {
           const int64_t idx = ((int64_t)b * K + k) * OHW + pix;
           if (vec && (idx & 7) == 0) {
-            v.v = *reinterpret_cast<const uint4*>(gy + idx);
+            v.raw = *reinterpret_cast<const uint4*>(gy + idx);
           } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v.e[j] = gy[idx + j];
@@ -261,25 +264,16 @@ struct GyRowsLoader {
 // contiguous along m, the accumulator fragments along n, so the tile goes
 // through LDS (Ct[n][m]) and each thread writes 8 consecutive pixels of
 // one channel: 16 bytes (bf16) or 2 x 16 bytes (fp32) where aligned.
-__device__ __forceinline__ void store8(bf16_t* dst, const float (&v)[8]) {
-  Chunk c;
+template <typename OutT>
+__device__ __forceinline__ void store8(OutT* dst, const float (&v)[8]) {
+  Vec<OutT, 8> c;  // rounded once, ahead of the branch
 #pragma unroll
-  for (int j = 0; j < 8; ++j) c.e[j] = f2bf(v[j]);
+  for (int j = 0; j < 8; ++j) from_f(v[j], c.e[j]);
   if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    *reinterpret_cast<uint4*>(dst) = c.v;
+    *reinterpret_cast<decltype(c.raw)*>(dst) = c.raw;
   } else {
 #pragma unroll
     for (int j = 0; j < 8; ++j) dst[j] = c.e[j];
-  }
-}
-
-__device__ __forceinline__ void store8(float* dst, const float (&v)[8]) {
-  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    reinterpret_cast<float4*>(dst)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4*>(dst)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dst[j] = v[j];
   }
 }
 

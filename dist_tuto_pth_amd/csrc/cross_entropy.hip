@@ -50,6 +50,9 @@
 // xent_finish_kernel (one block) sums row [B] and counts the rows not
 // ignored, thread i taking rows i, i+256, ... in ascending order, then a
 // fixed tree: the order depends on B alone.
+// The 8-element access (load_vec / store_vec), the chunk's tree (tree8) and
+// by_dtype are common.h's; xent_finish_kernel keeps block_sum's order
+// written out, because it reduces a float and an int in one pass.
 // xent_bwd_kernel is one pass with the forward's mapping: read x, write gx.
 // Limit: a row is never split across blocks, so a few very long rows (B far
 // below the number of CUs) use only B blocks of the chip.
@@ -63,12 +66,10 @@
 
 #include <cmath>
 #include <initializer_list>
-#include <type_traits>
 
 namespace {
 
 constexpr int CH = 8;             // elements per chunk
-constexpr int NWAVE = BLK / 64;
 constexpr int WAVE_MAX_N = 2048;  // above: a block per row (measured, see
                                   // profiles/cross_entropy_numbers.md)
 
@@ -88,45 +89,16 @@ __device__ __forceinline__ MS merge(MS a, MS b) {
   return MS{mn, __fadd_rn(__fmul_rn(a.s, fa), __fmul_rn(b.s, fb))};
 }
 
-__device__ __forceinline__ float tree8(const float* v) {
-  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-}
-
-// 8 consecutive elements at a 16-byte aligned address, in 16-byte accesses
-__device__ __forceinline__ void load8(const float* p, float* v) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void load8(const bf16_t* p, float* v) {
-  const uint4 a = *reinterpret_cast<const uint4*>(p);
-  v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-  v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-  v[4] = __uint_as_float(a.z << 16); v[5] = __uint_as_float(a.z & 0xffff0000u);
-  v[6] = __uint_as_float(a.w << 16); v[7] = __uint_as_float(a.w & 0xffff0000u);
-}
-__device__ __forceinline__ void store8(float* p, const float* v) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
-  uint4 a;
-  a.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-  a.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-  a.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-  a.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-  *reinterpret_cast<uint4*>(p) = a;
-}
-
 // The 8 values of chunk c of the row at xr: v[] for the exponentials (-inf
-// past N), z[] for the sum of x (0 past N).
+// past N), z[] for the sum of x (0 past N).  With VEC every row starts on a
+// 16-byte boundary, so a whole chunk is one aligned load_vec.
 template <typename T, bool VEC>
 __device__ __forceinline__ void load_chunk(const T* __restrict__ xr, int c,
-                                           int N, float* v, float* z) {
+                                           int N, float (&v)[CH],
+                                           float (&z)[CH]) {
   const int col0 = c * CH;
   if (VEC && col0 + CH <= N) {
-    load8(xr + col0, v);
+    load_vec<T, CH>(xr + col0, v);
 #pragma unroll
     for (int j = 0; j < CH; ++j) z[j] = v[j];
   } else {
@@ -278,6 +250,8 @@ __global__ __launch_bounds__(BLK) void xent_finish_kernel(
     s += row[i];
     c += target[i] != ignore ? 1 : 0;
   }
+  // block_sum's order, written out: the float and the int share one pass
+  // through LDS (two block_sum calls cost this one-block kernel 0.2 us)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     s += __shfl_down(s, o, 64);
@@ -295,7 +269,6 @@ __global__ __launch_bounds__(BLK) void xent_finish_kernel(
     count[0] = cnt;
   }
 }
-static_assert(NWAVE == 4, "xent_finish_kernel adds four waves");
 
 enum { RED_NONE = 0, RED_MEAN = 1, RED_SUM = 2 };
 
@@ -337,7 +310,7 @@ __global__ __launch_bounds__(BLK) void xent_bwd_kernel(
       for (int j = 0; j < CH; ++j) o[j] = 0.f;   // stored, not 0*g
     }
     if (VEC && col0 + CH <= N) {
-      store8(gr + col0, o);
+      store_vec<T, CH>(gr + col0, o);
     } else {
 #pragma unroll
       for (int j = 0; j < CH; ++j)
@@ -349,14 +322,6 @@ __global__ __launch_bounds__(BLK) void xent_bwd_kernel(
 // ===========================================================================
 // host launchers
 // ===========================================================================
-template <class F>
-void by_dtype(bool bf16, F&& f) {
-  if (bf16) f((bf16_t*)nullptr);
-  else f((float*)nullptr);
-}
-template <class P>
-using elem_t = std::remove_pointer_t<P>;
-
 // lanes per row from N alone; `mapping` 1 (lanes of a wave) or 2 (a block)
 // overrides the threshold, for measuring it
 int lanes_for(int64_t N, int mapping) {

@@ -43,14 +43,11 @@ __device__ __forceinline__ int lds_col(int row, int col) {
   return col ^ (((row >> 3) & 7) << 3);
 }
 
-union Chunk {  // 8 bf16
-  uint4 v;
-  bf16_t e[8];
-};
+using Chunk = Vec<bf16_t, 8>;  // 8 bf16 as one 16-byte value (common.h)
 
 __device__ __forceinline__ Chunk zero_chunk() {
   Chunk c;
-  c.v = make_uint4(0u, 0u, 0u, 0u);
+  c.raw = make_uint4(0u, 0u, 0u, 0u);
   return c;
 }
 
@@ -72,7 +69,7 @@ __device__ __forceinline__ void lds_store(bf16_t (*T)[LDS_LD], int tid,
     const int hi = chunk_hi(p, tid);
     const int lo = chunk_lo(tid);
     if (!TRANS) {
-      *reinterpret_cast<uint4*>(&T[hi][lds_col(hi, lo)]) = reg[p].v;
+      *reinterpret_cast<uint4*>(&T[hi][lds_col(hi, lo)]) = reg[p].raw;
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
@@ -97,10 +94,10 @@ __device__ __forceinline__ Chunk load8(const Operand& o, int64_t idx,
                                        int nvalid) {
   // nvalid = how many of the 8 consecutive elements from idx are in range
   Chunk c;
-  c.v = make_uint4(0u, 0u, 0u, 0u);
+  c.raw = make_uint4(0u, 0u, 0u, 0u);
   if (nvalid <= 0) return c;
   if (o.vec && nvalid >= 8) {
-    c.v = *reinterpret_cast<const uint4*>(o.p + idx);
+    c.raw = *reinterpret_cast<const uint4*>(o.p + idx);
     if (o.mask) {
       if (o.mask_f32) {
         const float4* m =
@@ -112,7 +109,7 @@ __device__ __forceinline__ Chunk load8(const Operand& o, int64_t idx,
         if (!(m1.z > 0.f)) c.e[6] = 0; if (!(m1.w > 0.f)) c.e[7] = 0;
       } else {
         Chunk m;
-        m.v = *reinterpret_cast<const uint4*>((const bf16_t*)o.mask + idx);
+        m.raw = *reinterpret_cast<const uint4*>((const bf16_t*)o.mask + idx);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if (!(to_f(m.e[j]) > 0.f)) c.e[j] = 0;

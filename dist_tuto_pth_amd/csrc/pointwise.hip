@@ -8,7 +8,9 @@
 // to_f() and written with from_f(), so both dtypes run the same index
 // arithmetic, the same RNG expression and the same mask writes; the only
 // per-type code is the pool's pair access (load_pair / store_pair).
-// Bindings take the dtype as a `bool bf16` before the stream.
+// Bindings take the dtype as a `bool bf16` before the stream and dispatch
+// on it with by_dtype; that, and the aligned vector access the bf16 pair
+// and the cast use (Vec, load_vec, store_vec), are common.h's.
 //
 // Grid-stride loops, 256-thread blocks, grids capped by grid_for().
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
@@ -17,8 +19,6 @@
 #include "common.h"
 
 #include <pybind11/pybind11.h>
-
-#include <type_traits>
 
 namespace {
 
@@ -44,15 +44,19 @@ __device__ __forceinline__ Pair<float> load_pair(const float* p) {
   return {p[0], p[1]};
 }
 __device__ __forceinline__ Pair<bf16_t> load_pair(const bf16_t* p) {
-  const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-  return {(bf16_t)(u & 0xffffu), (bf16_t)(u >> 16)};
+  Vec<bf16_t, 2> u;
+  u.raw = *reinterpret_cast<const uint32_t*>(p);
+  return {u.e[0], u.e[1]};
 }
 __device__ __forceinline__ void store_pair(float* p, Pair<float> v) {
   p[0] = v.a;
   p[1] = v.b;
 }
 __device__ __forceinline__ void store_pair(bf16_t* p, Pair<bf16_t> v) {
-  *reinterpret_cast<uint32_t*>(p) = (uint32_t)v.a | (uint32_t)v.b << 16;
+  Vec<bf16_t, 2> u;
+  u.e[0] = v.a;
+  u.e[1] = v.b;
+  *reinterpret_cast<uint32_t*>(p) = u.raw;
 }
 
 template <typename T>
@@ -218,17 +222,9 @@ __global__ void cast_f32_to_bf16_kernel(const float* __restrict__ src,
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nth = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < nvec; i += nth) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i];
-    const float4 b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    union {
-      uint4 v;
-      bf16_t e[8];
-    } c;
-    c.e[0] = f2bf(a.x); c.e[1] = f2bf(a.y);
-    c.e[2] = f2bf(a.z); c.e[3] = f2bf(a.w);
-    c.e[4] = f2bf(b.x); c.e[5] = f2bf(b.y);
-    c.e[6] = f2bf(b.z); c.e[7] = f2bf(b.w);
-    reinterpret_cast<uint4*>(dst)[i] = c.v;
+    float f[8];
+    load_vec<float, 8>(src + 8 * i, f);
+    store_vec<bf16_t, 8>(dst + 8 * i, f);
   }
   for (int64_t i = nvec * 8 + tid; i < n; i += nth) dst[i] = f2bf(src[i]);
 }
@@ -236,15 +232,6 @@ __global__ void cast_f32_to_bf16_kernel(const float* __restrict__ src,
 // ===========================================================================
 // host launchers
 // ===========================================================================
-// f(T*) with T the element type `bf16` names; the argument only carries T
-template <class F>
-void by_dtype(bool bf16, F&& f) {
-  if (bf16) f((bf16_t*)nullptr);
-  else f((float*)nullptr);
-}
-template <class P>
-using elem_t = std::remove_pointer_t<P>;
-
 // planes * (H/2) * (W/2); the bf16 kernels need whole 4-byte pairs
 int64_t pool_outputs(int B, int C, int H, int W, bool bf16) {
   if (bf16 && (H < 2 || W < 2 || (H & 1) || (W & 1)))

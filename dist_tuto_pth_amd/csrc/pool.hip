@@ -41,17 +41,19 @@
 //                          belongs to thread e % 256 and to its accumulator
 //                          (e / 256) % 4; the four are added as a fixed
 //                          tree, the lanes by shuffles, the waves through
-//                          LDS.
+//                          LDS (block_sum of common.h).
 //   gap_bwd_kernel         gx[b,c,:,:] = float(gy[b,c]) / (H*W): a streaming
-//                          write in 16-byte accesses between a scalar head
-//                          (up to gx's first 16-byte boundary) and tail.
+//                          write in 16-byte accesses (Vec of common.h)
+//                          between a scalar head (up to gx's first 16-byte
+//                          boundary) and tail.
 //   Both forward kernels read one element per access, so the order above is
 //   the only thing that decides the bits.  Limit: a plane is never split
 //   across blocks, so a few huge planes (B*C far below the number of CUs)
 //   use only B*C blocks of the chip.
 //
 // Grid-stride loops over int64 flat indices, 256-thread blocks, grids
-// capped by grid_for().  Bindings are registered from kernels.hip's
+// capped by grid_for(), launchers dispatched on the dtype by common.h's
+// by_dtype.  Bindings are registered from kernels.hip's
 // PYBIND11_MODULE through register_pool().
 
 #include "common.h"
@@ -60,11 +62,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 
 namespace {
 
-constexpr int NWAVE = BLK / 64;
 constexpr uint32_t WAVE_MAX_HW = 1024;  // above: a block per plane
 
 // ===========================================================================
@@ -291,17 +291,10 @@ __global__ __launch_bounds__(BLK) void gap_fwd_block_kernel(
     if (e < hw) a0 += to_f(xp[e]);
     if (e + BLK < hw) a1 += to_f(xp[e + BLK]);
     if (e + 2 * BLK < hw) a2 += to_f(xp[e + 2 * BLK]);
-    float v = (a0 + a1) + (a2 + a3);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();  // sh may still be read from the previous plane
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      from_f(((sh[0] + sh[1]) + (sh[2] + sh[3])) / cnt, y[pl]);
+    const float v = block_sum((a0 + a1) + (a2 + a3), sh);
+    if (threadIdx.x == 0) from_f(v / cnt, y[pl]);
   }
 }
-static_assert(NWAVE == 4, "gap_fwd_block_kernel adds four waves");
 
 template <typename T>
 __global__ __launch_bounds__(BLK) void gap_bwd_kernel(
@@ -316,10 +309,7 @@ __global__ __launch_bounds__(BLK) void gap_bwd_kernel(
     int64_t p = first / hw;
     uint32_t r = (uint32_t)(first - p * hw);
     float val = to_f(gy[p]) / cnt;
-    union {
-      uint4 raw;
-      T e[V];
-    } u;
+    Vec<T, V> u;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       if (r == hw) {  // the vector crosses into the next plane
@@ -342,15 +332,6 @@ __global__ __launch_bounds__(BLK) void gap_bwd_kernel(
 // ===========================================================================
 // host launchers
 // ===========================================================================
-// f(T*) with T the element type `bf16` names; the argument only carries T
-template <class F>
-void by_dtype(bool bf16, F&& f) {
-  if (bf16) f((bf16_t*)nullptr);
-  else f((float*)nullptr);
-}
-template <class P>
-using elem_t = std::remove_pointer_t<P>;
-
 // planes are indexed in 32 bits; the bound leaves room for the padded and
 // strided forms of the index ((H+1)*(W+1) outputs, hp + sh) in an int
 constexpr int64_t MAX_PLANE = (int64_t)1 << 29;

@@ -18,8 +18,8 @@ from dist_tuto_pth_amd import ops  # noqa: E402
 from dist_tuto_pth_amd.models.resnet import (Bottleneck, ResNet,  # noqa: E402
                                               resnet50)
 
-SHAPES = [(2, 3, 5, 7), (2, 5, 1, 1), (3, 70, 4, 4), (4, 8, 6, 6),
-          (2, 16, 14, 14), (5, 4, 7, 7), (64, 2, 20, 20)]
+SHAPES = [(2, 3, 5, 7), (2, 5, 1, 1), (2, 3, 2, 3), (3, 70, 4, 4),
+          (4, 8, 6, 6), (2, 16, 14, 14), (5, 4, 7, 7), (64, 2, 20, 20)]
 OFFSET_SHAPES = [(2, 3, 5, 7), (4, 8, 6, 6), (3, 70, 4, 4)]
 MODES = [(False, False), (False, True), (True, True)]
 DTYPES = [torch.float32, torch.bfloat16]

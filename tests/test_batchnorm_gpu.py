@@ -27,6 +27,7 @@ SPLIT_SHAPE = (64, 2, 20, 20)
 SHAPES = [
     (2, 3, 5, 7),        # odd HW = 35: one element per access
     (2, 5, 1, 1),        # n = 2, HW = 1
+    (2, 3, 2, 3),        # HW = 6: two elements per access in both dtypes
     (3, 70, 4, 4),       # C > 64, HW = 16
     (4, 8, 6, 6),        # bf16 planes only 8-byte aligned
     (2, 16, 14, 14),     # ResNet's 14x14 planes
