@@ -19,6 +19,63 @@
 
 namespace py = pybind11;
 
+// ---- argument structs ----------------------------------------------------
+// Plain aggregates of pointers and ints.  Who takes them, in one place:
+//  - the host layer holds NetWs / GwPtrs and passes them, or their typed
+//    members, to every launch;
+//  - net_fused_fwdbwd_kernel and the two net_gw_partial_fold_kernel take
+//    them by value;
+//  - every other kernel and every device helper keeps a __restrict__
+//    pointer list.  The helpers because the stashes mix floats with bytes
+//    (idx1, m2, idx2, m3): a byte access may alias anything unless its
+//    pointer is a __restrict__ PARAMETER, which neither a struct member
+//    nor a local can be, and without it merged accesses split up.  The
+//    kernels because each was slower, or spilled, with struct arguments
+//    (profiles/net_fused_args.md has the figures).
+//
+// Per-batch workspace of the fused step (allocated by ops/fused.py).
+// It crosses the binding as ONE pointer vector; NET_WS_FIELDS is the
+// only definition of its order (exported as `ws_fields`).
+static const char* const NET_WS_FIELDS[] = {
+    "p1", "idx1", "m2", "p2", "idx2", "h1", "m3", "d3", "logp", "glog",
+    "gh1", "ga2", "ga1", "part", "loss_part", "loss"};
+constexpr int NET_WS_N = sizeof(NET_WS_FIELDS) / sizeof(NET_WS_FIELDS[0]);
+
+struct NetWs {
+  float* p1;         // [B,1440] pool1 out
+  uint8_t* idx1;     // [B,1440] pool1 argmax (bit 2: relu cut it)
+  uint8_t* m2;       // [B,20]   dropout2d keep mask
+  float* p2;         // [B,320]  pool2 out
+  uint8_t* idx2;     // [B,320]
+  float* h1;         // [B,50]   fc1 out (post relu)
+  uint8_t* m3;       // [B,50]   dropout keep mask
+  float* d3;         // [B,50]   fc1 out after dropout
+  float* logp;       // [B,10]
+  float* glog;       // [B,10]   fc2 out grad
+  float* gh1;        // [B,50]   fc1 pre-relu grad
+  float* ga2;        // [B,1280] conv2 out grad
+  float* ga1;        // [B,5760] conv1 out grad
+  float* part;       // [GW_MAX_CH][GW_ROW] weight-gradient partials
+  float* loss_part;  // [fwd grid] per-block loss partials
+  float* loss;       // scalar
+};
+static_assert(sizeof(NetWs) == NET_WS_N * sizeof(void*),
+              "NetWs has one pointer per NET_WS_FIELDS name, same order");
+
+// The 8 per-parameter pointers (weights, gradients or momentum buffers;
+// they may alias one flat buffer), slots in the order of the flat
+// gradient layout OFF_W1 .. OFF_BF2.
+struct GwPtrs { float* p[8]; };
+enum { G_W1, G_B1, G_W2, G_B2, G_WF1, G_BF1, G_WF2, G_BF2 };
+
+// A step's inputs (the fwd+bwd kernel's; its loss gradient is 1).
+struct NetIn {
+  const float* x;                  // [B,1,28,28]
+  const int64_t* tgt;              // [B]
+  const unsigned long long* seed;  // device dropout seed
+  int B, training;
+};
+
 // fused step prologue: advance the dropout seed (when training) and
 // zero the loss accumulator in ONE tiny launch instead of a bump
 // kernel + a hipMemsetAsync fill kernel (each ~4.5 us of pure launch
@@ -667,6 +724,9 @@ __device__ __forceinline__ void net_bwd_sample(
 __global__ void
 __launch_bounds__(256)
 net_fused_bwd_kernel(
+    // pointer by pointer, not NetWs by value: the struct form measured
+    // slower in the tiled kernel (profiles/net_fused_args.md), and the
+    // host picks between the two through one function pointer
     const float* __restrict__ w2, const float* __restrict__ wf1,
     const float* __restrict__ wf2,
     const int64_t* __restrict__ tgt,
@@ -915,26 +975,12 @@ net_fused_bwd_tiled_kernel(
 // + 7168 floats = 47.7 KB/WG -> 3 WGs/CU.
 __global__ void
 __launch_bounds__(256)
-net_fused_fwdbwd_kernel(
-    const float* __restrict__ x,
-    const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w2, const float* __restrict__ b2,
-    const float* __restrict__ wf1, const float* __restrict__ bf1,
-    const float* __restrict__ wf2, const float* __restrict__ bf2,
-    const int64_t* __restrict__ tgt,
-    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
-    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
-    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
-    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
-    float* __restrict__ logp_ws,
-    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
-    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,
-    float* __restrict__ loss_part,
-    const unsigned long long* __restrict__ seed_p, int B, int training) {
+net_fused_fwdbwd_kernel(NetIn in, GwPtrs prm, NetWs ws) {
   __shared__ __attribute__((aligned(16))) float w2s[N_C2K * 250 + N_C2K];
   __shared__ __attribute__((aligned(16))) float pool[7168];
   const int tid = threadIdx.x;
-  const uint64_t seed = seed_p[0];
+  const int B = in.B;
+  const uint64_t seed = in.seed[0];
   // forward carve
   float* xs = pool;              // 784
   float* w1s = pool + 784;       // 260
@@ -953,19 +999,20 @@ net_fused_fwdbwd_kernel(
   float lsum = 0.f;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const float lp_t = net_fwd_sample(
-        b, tid, B, training, seed, 0, nullptr, 0u, x, w1, b1, w2, b2,
-        wf1,
-        bf1, wf2, bf2, tgt, p1_ws, idx1_ws, m2_ws, p2_ws, idx2_ws,
-        h1_ws, m3_ws, d3_ws, logp_ws, xs, w1s, p1, w2s, p2, d3, logits);
+        b, tid, B, in.training, seed, 0, nullptr, 0u, in.x, prm.p[G_W1],
+        prm.p[G_B1], prm.p[G_W2], prm.p[G_B2], prm.p[G_WF1], prm.p[G_BF1],
+        prm.p[G_WF2], prm.p[G_BF2], in.tgt, ws.p1, ws.idx1, ws.m2, ws.p2,
+        ws.idx2, ws.h1, ws.m3, ws.d3, ws.logp, xs, w1s, p1, w2s, p2, d3,
+        logits);
     if (tid == 0) lsum += -lp_t / B;
     __syncthreads();  // fwd LDS dead + this block's global stashes visible
-    net_bwd_sample(b, 0, 1, tid, B, training, sc, wf1, wf2, tgt,
-                   idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws, logp_ws,
-                   glog_ws, gh1_ws, ga2_ws, ga1_ws,
+    net_bwd_sample(b, 0, 1, tid, B, in.training, sc, prm.p[G_WF1],
+                   prm.p[G_WF2], in.tgt, ws.idx1, ws.m2, ws.idx2, ws.h1,
+                   ws.m3, ws.logp, ws.glog, ws.gh1, ws.ga2, ws.ga1,
                    w2s, glg, gd3, gh1, gp2, gd2p);
     __syncthreads();  // bwd LDS dead before the next sample reuses pool
   }
-  if (tid == 0) loss_part[blockIdx.x] = lsum;
+  if (tid == 0) ws.loss_part[blockIdx.x] = lsum;
 }
 
 // Per-chunk partial weight gradients for all four layers in ONE launch
@@ -1262,7 +1309,10 @@ __device__ __forceinline__ void net_gw_tile(
 }
 
 __global__ void __launch_bounds__(256)
-net_gw_partial_kernel(const float* __restrict__ x,
+net_gw_partial_kernel(// pointer by pointer: with NetWs by value this kernel
+                      // measured 0.2-0.7 us slower
+                      // (profiles/net_fused_args.md)
+                      const float* __restrict__ x,
                       const float* __restrict__ p1_ws,
                       const float* __restrict__ p2_ws,
                       const float* __restrict__ d3_ws,
@@ -1290,7 +1340,6 @@ net_gw_partial_kernel(const float* __restrict__ x,
 
 // combine: grads[i] = sum over chunks of part[c][i], written through
 // the 8 per-parameter pointers (which may alias one flat buffer).
-struct GwPtrs { float* p[8]; };
 // sum flat-grad element i over the nch chunk rows (+ conv1 extension)
 template <bool SC1 = false>
 __device__ __forceinline__ float net_gw_combine_elem(
@@ -1508,25 +1557,18 @@ __device__ __forceinline__ void net_gw_fold_range(
 
 template <bool DO_SGD>
 __global__ void __launch_bounds__(256)
-net_gw_partial_fold_kernel(const float* __restrict__ x,
-                           const float* __restrict__ p1_ws,
-                           const float* __restrict__ p2_ws,
-                           const float* __restrict__ d3_ws,
-                           const float* __restrict__ ga1_ws,
-                           const float* __restrict__ ga2_ws,
-                           const float* __restrict__ gh1_ws,
-                           const float* __restrict__ glog_ws,
-                           float* __restrict__ part, int B, int bchunk,
+net_gw_partial_fold_kernel(const float* __restrict__ x, NetWs ws, int B,
+                           int bchunk,
                            GwPtrs g, GwPtrs prm, GwPtrs buf, float lr,
                            float mu, const float* __restrict__ loss_part,
                            float* __restrict__ loss_out, int nblk_fwd,
                            unsigned long long* seed_bump,
                            unsigned int* __restrict__ cnt) {
   const int b0 = blockIdx.y * bchunk;
+  float* __restrict__ part = ws.part;
   net_gw_tile<true>(blockIdx.x, threadIdx.x, b0, min(B, b0 + bchunk),
-                    part + (int64_t)blockIdx.y * GW_ROW,
-                    x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws,
-                    glog_ws);
+                    part + (int64_t)blockIdx.y * GW_ROW, x, ws.p1, ws.p2,
+                    ws.d3, ws.ga1, ws.ga2, ws.gh1, ws.glog);
   // ---- last-arriver ticket, FENCE-FREE: the tile wrote its partials
   // with sc1 stores (already at the coherence point once vmcnt
   // retires), so the ticket needs only the vmcnt drain before it and
@@ -1613,6 +1655,8 @@ namespace cg = cooperative_groups;
 
 __global__ void __launch_bounds__(256)
 net_step_kernel(
+    // (with NetWs by value its pointers are all loaded at entry and held:
+    // at 256 VGPRs and occupancy 1 that spilled SGPRs to VGPR lanes)
     const float* __restrict__ x,
     const int64_t* __restrict__ tgt,
     const float* __restrict__ gl,
@@ -1650,10 +1694,10 @@ net_step_kernel(
   const int wg = blockIdx.x, nblk = gridDim.x;
   cg::grid_group grid = cg::this_grid();
 
-  const float* w1 = prm.p[0]; const float* b1 = prm.p[1];
-  const float* w2 = prm.p[2]; const float* b2 = prm.p[3];
-  const float* wf1 = prm.p[4]; const float* bf1 = prm.p[5];
-  const float* wf2 = prm.p[6]; const float* bf2 = prm.p[7];
+  const float* w1 = prm.p[G_W1]; const float* b1 = prm.p[G_B1];
+  const float* w2 = prm.p[G_W2]; const float* b2 = prm.p[G_B2];
+  const float* wf1 = prm.p[G_WF1]; const float* bf1 = prm.p[G_BF1];
+  const float* wf2 = prm.p[G_WF2]; const float* bf2 = prm.p[G_BF2];
   const uint64_t seed = seed_p[0];
 
   // ---- phase 1: forward ------------------------------------------------
@@ -1727,22 +1771,7 @@ net_step_kernel(
 namespace {
 
 // ---- fused Net step: host layer -------------------------------------------
-// Per-batch workspace of the fused step (allocated by ops/fused.py).
-// It crosses the binding as ONE pointer vector; NET_WS_FIELDS is the
-// only definition of its order (exported as `ws_fields`).
-static const char* const NET_WS_FIELDS[] = {
-    "p1", "idx1", "m2", "p2", "idx2", "h1", "m3", "d3", "logp", "glog",
-    "gh1", "ga2", "ga1", "part", "loss_part", "loss"};
-constexpr int NET_WS_N = sizeof(NET_WS_FIELDS) / sizeof(NET_WS_FIELDS[0]);
-
-struct NetWs {
-  float* p1; uint8_t* idx1; uint8_t* m2; float* p2; uint8_t* idx2;
-  float* h1; uint8_t* m3; float* d3; float* logp; float* glog; float* gh1;
-  float* ga2; float* ga1; float* part; float* loss_part; float* loss;
-};
-static_assert(sizeof(NetWs) == NET_WS_N * sizeof(void*),
-              "NetWs has one pointer per NET_WS_FIELDS name, same order");
-
+// the workspace's pointer vector, in NET_WS_FIELDS order
 static NetWs net_ws(const std::vector<uintptr_t>& v) {
   if ((int)v.size() != NET_WS_N)
     throw std::runtime_error("net workspace: expected " +
@@ -1767,6 +1796,20 @@ static GwPtrs buf_ptrs(const std::vector<uintptr_t>& v) {
   GwPtrs g{};
   for (int i = 0; i < 8 && i < (int)v.size(); ++i) g.p[i] = (float*)v[i];
   return g;
+}
+
+// a per-device u32 buffer of n entries, allocated and zeroed once
+// (bufs: the caller's function-local static, one slot per device)
+static unsigned int* zeroed_once(unsigned int* (&bufs)[64], size_t n,
+                                 hipStream_t s) {
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
+  if (!bufs[dev]) {
+    HIP_CHECK(hipMalloc(&bufs[dev], n * sizeof(unsigned int)));
+    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, n * sizeof(unsigned int), s));
+  }
+  return bufs[dev];
 }
 
 // integer environment variable (0 when unset); callers that may read
@@ -1829,15 +1872,7 @@ static GwPlan gw_plan(int B) {
 // zeroed once; each reducer re-arms its own counter every step)
 static unsigned int* gw_cnt_buf(hipStream_t s) {
   static unsigned int* bufs[64] = {};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
-  if (!bufs[dev]) {
-    HIP_CHECK(hipMalloc(&bufs[dev], GW_TILES * sizeof(unsigned int)));
-    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, GW_TILES * sizeof(unsigned int),
-                             s));
-  }
-  return bufs[dev];
+  return zeroed_once(bufs, GW_TILES, s);
 }
 
 // fwd sibling split: 2 workgroups per sample when one per sample
@@ -1875,15 +1910,7 @@ static unsigned int fwd_token() {
 // once; published tokens are step-unique, no re-arm needed)
 static unsigned int* fwd_flags_buf(hipStream_t s) {
   static unsigned int* bufs[64] = {};
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
-  if (!bufs[dev]) {
-    HIP_CHECK(hipMalloc(&bufs[dev], 4096 * sizeof(unsigned int)));
-    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, 4096 * sizeof(unsigned int),
-                             s));
-  }
-  return bufs[dev];
+  return zeroed_once(bufs, 4096, s);
 }
 
 // Seed convention of every fused path: a training step CONSUMES the
@@ -1908,13 +1935,12 @@ void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
   if (!use_loss_part)
     hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0,
                        S(stream), (unsigned long long*)nullptr, w.loss);
+  // the two forward kernels share their leading parameters
   auto launch = [&](auto kern, int grid, auto... extra) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, S(stream),
-                       (const float*)x, (const float*)prm.p[0],
-                       (const float*)prm.p[1], (const float*)prm.p[2],
-                       (const float*)prm.p[3], (const float*)prm.p[4],
-                       (const float*)prm.p[5], (const float*)prm.p[6],
-                       (const float*)prm.p[7], (const int64_t*)tgt, w.p1,
+                       (const float*)x, prm.p[G_W1], prm.p[G_B1],
+                       prm.p[G_W2], prm.p[G_B2], prm.p[G_WF1], prm.p[G_BF1],
+                       prm.p[G_WF2], prm.p[G_BF2], (const int64_t*)tgt, w.p1,
                        w.idx1, w.m2, w.p2, w.idx2, w.h1, w.m3, w.d3, w.logp,
                        w.loss, loss_part,
                        (const unsigned long long*)seed_dev, B,
@@ -1961,11 +1987,9 @@ static void launch_bwd_data(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
   hipLaunchKernelGGL(kern, dim3(grid_for((int64_t)B * split, 1)),
                      dim3(bwd_tiled() ? BT_NT : 256), 0, s,
                      (const float*)w2, (const float*)wf1, (const float*)wf2,
-                     (const int64_t*)tgt, (const float*)gl,
-                     (const uint8_t*)w.idx1, (const uint8_t*)w.m2,
-                     (const uint8_t*)w.idx2, (const float*)w.h1,
-                     (const uint8_t*)w.m3, (const float*)w.logp, w.glog,
-                     w.gh1, w.ga2, w.ga1, B, training ? 1 : 0, split);
+                     (const int64_t*)tgt, (const float*)gl, w.idx1, w.m2,
+                     w.idx2, w.h1, w.m3, w.logp, w.glog, w.gh1, w.ga2, w.ga1,
+                     B, training ? 1 : 0, split);
 }
 
 // Weight gradients, the end of every multi-dispatch step: one segmented
@@ -1982,22 +2006,15 @@ static void launch_gw(const float* x, const NetWs& w, int B, GwPtrs gp,
   if (gw_fold_on()) {
     auto* kern = !sgd ? net_gw_partial_fold_kernel<false>
                       : net_gw_partial_fold_kernel<true>;
-    hipLaunchKernelGGL(kern, dim3(GW_TILES, pl.nch), dim3(256), 0, s, x,
-                       (const float*)w.p1, (const float*)w.p2,
-                       (const float*)w.d3, (const float*)w.ga1,
-                       (const float*)w.ga2, (const float*)w.gh1,
-                       (const float*)w.glog, w.part, B, pl.bchunk, gp, pp,
-                       bp, lr, mu, loss_part, loss_out, nblk_fwd, seed,
-                       gw_cnt_buf(s));
+    hipLaunchKernelGGL(kern, dim3(GW_TILES, pl.nch), dim3(256), 0, s, x, w,
+                       B, pl.bchunk, gp, pp, bp, lr, mu, loss_part,
+                       loss_out, nblk_fwd, seed, gw_cnt_buf(s));
     return;
   }
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, pl.gy),
-                     dim3(256), 0, s, x, (const float*)w.p1,
-                     (const float*)w.p2, (const float*)w.d3,
-                     (const float*)w.ga1, (const float*)w.ga2,
-                     (const float*)w.gh1, (const float*)w.glog, w.part, B,
-                     pl.bchunk, pl.bchunk1, pl.bchunk2, pl.nch, pl.nch1,
-                     pl.nch2, 0);
+                     dim3(256), 0, s, x, w.p1, w.p2, w.d3, w.ga1, w.ga2,
+                     w.gh1, w.glog, w.part, B, pl.bchunk, pl.bchunk1,
+                     pl.bchunk2, pl.nch, pl.nch1, pl.nch2, 0);
   const dim3 grid((GW_TOTAL * 4 + 255) / 256);
   if (!sgd)
     hipLaunchKernelGGL(net_gw_combine_kernel, grid, dim3(256), 0, s,
@@ -2081,15 +2098,11 @@ void net_fused_fwdbwd(uintptr_t x, const std::vector<uintptr_t>& wts_v,
                         : GwPtrs{};
   const int nblk = grid_for(B, 1);
   hipLaunchKernelGGL(net_fused_fwdbwd_kernel, dim3(nblk), dim3(256), 0,
-                     S(stream), (const float*)x, (const float*)wt.p[0],
-                     (const float*)wt.p[1], (const float*)wt.p[2],
-                     (const float*)wt.p[3], (const float*)wt.p[4],
-                     (const float*)wt.p[5], (const float*)wt.p[6],
-                     (const float*)wt.p[7], (const int64_t*)tgt, w.p1,
-                     w.idx1, w.m2, w.p2, w.idx2, w.h1, w.m3, w.d3, w.logp,
-                     w.glog, w.gh1, w.ga2, w.ga1, w.loss_part,
-                     (const unsigned long long*)seed_dev, B,
-                     training ? 1 : 0);
+                     S(stream),
+                     NetIn{(const float*)x, (const int64_t*)tgt,
+                           (const unsigned long long*)seed_dev, B,
+                           training ? 1 : 0},
+                     wt, w);
   launch_gw((const float*)x, w, B, gp, pp, buf_ptrs(buf_v), (float)lr,
             (float)mu, sgd, w.loss_part, w.loss, nblk,
             seed_bump(training, seed_dev), S(stream));
@@ -2112,8 +2125,7 @@ void net_gw_combine_raw(uintptr_t part_ws,
                         const std::vector<uintptr_t>& grd_v, int nch,
                         int nch1, int nch2,
                         uintptr_t stream) {
-  GwPtrs gp{};
-  for (int i = 0; i < 8; ++i) gp.p[i] = (float*)grd_v[i];
+  const GwPtrs gp = gw_ptrs(grd_v, "net_gw_combine_raw grads");
   hipLaunchKernelGGL(net_gw_combine_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, nch, nch1,
@@ -2130,15 +2142,12 @@ void net_gw_combine_sgd_raw(uintptr_t part_ws,
                             double mu,
                             uintptr_t loss_part, uintptr_t loss_out,
                             int nblk_fwd, uintptr_t stream) {
-  GwPtrs gp{}, pp{}, bp{};
-  for (int i = 0; i < 8; ++i) {
-    gp.p[i] = (float*)grd_v[i];
-    pp.p[i] = (float*)prm_v[i];
-    bp.p[i] = (i < (int)buf_v.size()) ? (float*)buf_v[i] : nullptr;
-  }
+  const GwPtrs gp = gw_ptrs(grd_v, "net_gw_combine_sgd_raw grads");
+  const GwPtrs pp = gw_ptrs(prm_v, "net_gw_combine_sgd_raw params");
   hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
                      dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
-                     S(stream), (const float*)part_ws, gp, pp, bp, nch,
+                     S(stream), (const float*)part_ws, gp, pp,
+                     buf_ptrs(buf_v), nch,
                      nch1, nch2, (float)lr, (float)mu,
                      (const float*)loss_part, (float*)loss_out,
                      nblk_fwd, nullptr);
@@ -2196,6 +2205,19 @@ int net_step_max_blocks() {
 
 bool net_step_available() { return net_step_max_blocks() > 0; }
 
+// Cooperative launch with the void* argument array built here.  P comes
+// from the kernel's signature alone (common_type_t keeps it out of
+// deduction at the arguments), so the call is checked like a direct call
+// of the kernel: a missing, extra or unconvertible argument does not
+// compile, and each is converted to its parameter's exact type.
+template <class... P>
+static void launch_coop(void (*kern)(P...), dim3 grid, dim3 block,
+                        hipStream_t s, std::common_type_t<P>... a) {
+  void* args[] = {&a...};
+  HIP_CHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(kern),
+                                       grid, block, args, 0, s));
+}
+
 void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
               const std::vector<uintptr_t>& ws_v, uintptr_t seed_dev,
               const std::vector<uintptr_t>& prm_v,
@@ -2207,29 +2229,21 @@ void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
   if (nblk < 1)
     throw std::runtime_error(
         "net_step: cooperative launch unavailable on this device");
-  NetWs w = net_ws(ws_v);
-  GwPtrs prm = gw_ptrs(prm_v, "net_step params");
-  GwPtrs grd = gw_ptrs(grd_v, "net_step grads");
-  GwPtrs buf = buf_ptrs(buf_v);
   int split = 1;
   while (split < 8 && B * split < nblk) split *= 2;
   // its own chunking: uniform, as many of the part rows as B fills
-  int bchunk = (B + GW_MAX_CH - 1) / GW_MAX_CH;
-  int nch = (B + bchunk - 1) / bchunk;
-  const float* xp = (const float*)x;
-  const int64_t* tgtp = (const int64_t*)tgt;
-  const float* glp = (const float*)gl;
-  unsigned long long* seedp = (unsigned long long*)seed_dev;
-  float lrf = (float)lr, muf = (float)mu;
-  int do_sgd_i = do_sgd ? 1 : 0, Bi = B, tri = training ? 1 : 0;
-  void* args[] = {&xp, &tgtp, &glp, &w.p1, &w.idx1, &w.m2, &w.p2, &w.idx2,
-                  &w.h1, &w.m3, &w.d3, &w.logp, &w.glog, &w.gh1, &w.ga2,
-                  &w.ga1, &w.part, &w.loss_part, &w.loss, &seedp, &prm,
-                  &grd, &buf, &lrf, &muf, &do_sgd_i, &Bi, &tri, &split,
-                  &bchunk, &nch};
-  HIP_CHECK(hipLaunchCooperativeKernel(
-      reinterpret_cast<const void*>(net_step_kernel), dim3(nblk),
-      dim3(256), args, 0, S(stream)));
+  const int bchunk = (B + GW_MAX_CH - 1) / GW_MAX_CH;
+  const int nch = (B + bchunk - 1) / bchunk;
+  const NetWs w = net_ws(ws_v);
+  launch_coop(net_step_kernel, dim3(nblk), dim3(256), S(stream),
+              (const float*)x, (const int64_t*)tgt, (const float*)gl, w.p1,
+              w.idx1, w.m2, w.p2, w.idx2, w.h1, w.m3, w.d3, w.logp, w.glog,
+              w.gh1, w.ga2, w.ga1, w.part, w.loss_part, w.loss,
+              (unsigned long long*)seed_dev,
+              gw_ptrs(prm_v, "net_step params"),
+              gw_ptrs(grd_v, "net_step grads"), buf_ptrs(buf_v), (float)lr,
+              (float)mu, do_sgd ? 1 : 0, B, training ? 1 : 0, split, bchunk,
+              nch);
 }
 }  // namespace
 

@@ -184,3 +184,22 @@ def test_gw_chunk_plan_and_exported_constants():
         for fam in ("", "1", "2"):
             assert pl["bchunk" + fam] == -(-B // pl["nch" + fam]), (B, pl)
         assert pl["gy"] == max(nchs)
+
+
+def test_gw_combine_raw_checks_pointer_counts():
+    """The raw combine launchers take their eight gradient (and
+    parameter) pointers through the same size check as every other
+    binding: a short vector raises before anything is launched, so the
+    check needs no GPU."""
+    import pytest
+    from dist_tuto_pth_amd.utils.native import load_native
+    k = load_native("_kernels")
+    eight, seven = [0] * 8, [0] * 7
+    with pytest.raises(RuntimeError, match="expected 8 pointers"):
+        k.net_gw_combine_raw(0, seven, 1, 1, 1, 0)
+    with pytest.raises(RuntimeError, match="expected 8 pointers"):
+        k.net_gw_combine_sgd_raw(0, seven, eight, [], 1, 1, 1, 0.01, 0.5,
+                                 0, 0, 0, 0)
+    with pytest.raises(RuntimeError, match="expected 8 pointers"):
+        k.net_gw_combine_sgd_raw(0, eight, seven, [], 1, 1, 1, 0.01, 0.5,
+                                 0, 0, 0, 0)
