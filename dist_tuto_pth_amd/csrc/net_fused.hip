@@ -1379,131 +1379,238 @@ __device__ __forceinline__ float net_gw_combine_elem(
   return (a0 + a1) + (a2 + a3);
 }
 
-// quad-lane variant: four consecutive lanes cooperate on one flat-grad
-// element (lane q strides the chunk rows), combined with two xor
-// shuffles.  Quadruples the wave count of the combine kernels — at 86
-// one-element-per-thread blocks they left 2/3 of the SIMDs empty and
-// ran a latency-exposed 8-deep L2 chain (profiles/).  Returns the full
-// sum on EVERY lane of the quad (butterfly reduction).
-__device__ __forceinline__ float net_gw_combine_elem_quad(
-    int i, int q, int nch, int nch1, int nch2,
-    const float* __restrict__ part) {
-  const int n = i < 260 ? nch1
-              : (i >= OFF_W2 && i < OFF_WF1) ? nch2 : nch;
-  float a0 = 0.f, a1 = 0.f;
-  for (int c = q; c < n; c += 8)
-    a0 += part[(int64_t)c * GW_ROW + i];
-  for (int c = q + 4; c < n; c += 8)
-    a1 += part[(int64_t)c * GW_ROW + i];
-  if (i < 260) {  // conv1 extension rows, spread across the quad
-    // fully unrolled (see net_gw_combine_elem note)
-    if (q == 0) {
-      for (int c2 = 0; c2 < nch1; ++c2) {
-        const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-        a0 += ext[i] + ext[260 + i] + ext[2 * 260 + i] + ext[3 * 260 + i];
-        a1 += ext[4 * 260 + i] + ext[5 * 260 + i] + ext[6 * 260 + i];
-      }
-    }
-  }
-  float acc = a0 + a1;
-  acc += __shfl_xor(acc, 1, 4);
-  acc += __shfl_xor(acc, 2, 4);
-  return acc;
-}
-
 __device__ __forceinline__ int net_gw_tensor_of(int i, const int* off) {
   int t = 0;
   while (i >= off[t + 1]) ++t;
   return t;
 }
 
-// finalize the per-block loss partials written by the forward kernel
-// (loss_part mode) and advance the dropout seed for the NEXT step —
-// runs in block 0 of a combine kernel, replacing the step-prologue
-// dispatch (~4.5 us device floor) entirely.  The seed convention is
-// bump-AFTER everywhere (both the loss_part and the legacy autograd
-// path): the step consumes the current seed, the combine advances it.
-__device__ __forceinline__ void net_loss_finalize(
-    const float* __restrict__ loss_part, float* __restrict__ loss_out,
-    int nblk_fwd, unsigned long long* seed_bump) {
-  if (loss_part) {
-    __shared__ float red[256];
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nblk_fwd; i += 256) v += loss_part[i];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    #pragma unroll
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-      if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss_out = red[0];
-  }
-  if (threadIdx.x == 0 && seed_bump)
-    *seed_bump += SEED_INC;
+// ---------------------------------------------------------------------------
+// The combine dispatch: grads[i] = sum over chunk rows of part[c][i],
+// optionally followed by the SGD+momentum update, plus the loss
+// finalise and the seed advance.  Its work is tiny (about 2 MB read), so
+// its time is the number of DEPENDENT memory round trips on its longest
+// path.  Every block therefore issues all of its loads (partial rows,
+// momentum, parameter) before its first wait: the row loops have
+// compile-time bounds, and a row past the family's chunk count is
+// CLAMPED to the last live row and its value replaced by 0 (a branch
+// around a load makes hipcc wait per load; a clamped load hits the line
+// a neighbour already fetched).  Rows >= n are never read.
+//
+// Grid (net_gw_combine_grid): [conv1 x GW_CB_C1 | loss | seed | main].
+//   conv1 block: 16 consecutive elements of [0,260) x 16 row groups.
+//     An element sums nch1 * T_CONV1 slots (sub 0 in the canonical
+//     region, subs 1-7 in the extension); group r takes slot r & 7 of
+//     chunk rows 2k + (r >> 3), k = 0..15.  The element index is
+//     fastest across lanes, so 16 lanes read one 64-byte segment.
+//   loss block: sums loss_part; seed block: advances the seed.  On
+//     their own so that no gradient element waits behind them, nor the
+//     loss behind the seed's round trip.
+//   main block: elements [260, GW_TOTAL), 4 lanes each; lane q takes
+//     rows q + 4k, k = 0..7.
+// All sums run in a fixed order (no atomics): deterministic.
+#define GW_MAX_CH 32      // rows of the part workspace
+#define GW_CB_C1 ((260 + 15) / 16)
+#define GW_CB_MAIN (((GW_TOTAL - 260) * 4 + 255) / 256)
+static_assert(T_CONV1 == 8 && GW_MAX_CH == 32,
+              "conv1 block: 16 groups x 16 rows cover 32 chunks x 8 slots");
+
+static inline dim3 net_gw_combine_grid() {
+  return dim3(GW_CB_C1 + 2 + GW_CB_MAIN);
 }
 
-__global__ void net_gw_combine_kernel(const float* __restrict__ part,
-                                      GwPtrs g, int nch, int nch1,
-                                      int nch2,
-                                      const float* __restrict__ loss_part,
-                                      float* __restrict__ loss_out,
-                                      int nblk_fwd,
-                                      unsigned long long* seed_bump) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int64_t t4 = blockIdx.x * blockDim.x + threadIdx.x;
-       t4 < (int64_t)GW_TOTAL * 4;
-       t4 += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
-    const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               part);
-    if (q == 0) {
-      const int t = net_gw_tensor_of(i, off);
-      g.p[t][i - off[t]] = acc;
-    }
+// Pointer of flat-grad element i in its own tensor (null when the
+// tensor's pointer is null), for i in the conv1 region (C1) or past it:
+// compile-time comparisons, constant indices.  gw_pin keeps a pointer
+// in scalar registers; left alone, hipcc turns the select chain back
+// into one indexed load from the kernarg segment, a memory round trip
+// that every later load waits for.  The result is typed as global
+// memory, which the pin would otherwise hide (flat instead of global
+// loads and stores).
+typedef __attribute__((address_space(1))) float gw_gfloat;
+
+__device__ __forceinline__ gw_gfloat* gw_pin(float* q) {
+  asm volatile("" : "+s"(q));
+  return (gw_gfloat*)q;
+}
+
+template <bool C1>
+__device__ __forceinline__ gw_gfloat* net_gw_ptr_of(const GwPtrs& p,
+                                                    int i) {
+  gw_gfloat* b;
+  int o;
+  if (C1) {
+    gw_gfloat* const w1 = gw_pin(p.p[0]), * const b1 = gw_pin(p.p[1]);
+    b = i < OFF_B1 ? w1 : b1;
+    o = i < OFF_B1 ? OFF_W1 : OFF_B1;
+  } else {
+    gw_gfloat* const w2 = gw_pin(p.p[2]), * const b2 = gw_pin(p.p[3]);
+    gw_gfloat* const wf1 = gw_pin(p.p[4]), * const bf1 = gw_pin(p.p[5]);
+    gw_gfloat* const wf2 = gw_pin(p.p[6]), * const bf2 = gw_pin(p.p[7]);
+    b = w2, o = OFF_W2;
+    if (i >= OFF_B2) b = b2, o = OFF_B2;
+    if (i >= OFF_WF1) b = wf1, o = OFF_WF1;
+    if (i >= OFF_BF1) b = bf1, o = OFF_BF1;
+    if (i >= OFF_WF2) b = wf2, o = OFF_WF2;
+    if (i >= OFF_BF2) b = bf2, o = OFF_BF2;
   }
-  if ((loss_part || seed_bump) && blockIdx.x == 0)
-    net_loss_finalize(loss_part, loss_out, nblk_fwd, seed_bump);
+  return b ? b + (i - o) : nullptr;
+}
+
+// one output element: its three addresses, and the momentum and
+// parameter values, whose loads are issued here, ahead of the row loads
+struct GwElem { gw_gfloat* g; gw_gfloat* prm; gw_gfloat* buf; float b, p; };
+
+template <bool SGD, bool C1>
+__device__ __forceinline__ GwElem net_gw_elem_open(
+    int i, const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf) {
+  GwElem e{net_gw_ptr_of<C1>(g, i), nullptr, nullptr, 0.f, 0.f};
+  if (SGD) {
+    e.prm = net_gw_ptr_of<C1>(prm, i);
+    e.buf = net_gw_ptr_of<C1>(buf, i);
+    e.p = *e.prm;
+    e.b = *(e.buf ? e.buf : e.prm);  // no buffer: any valid address
+    // the loads stay HERE: without this, hipcc sinks them into the
+    // branch of the one lane that stores, behind the row loads' wait
+    asm volatile("" ::: "memory");
+  }
+  return e;
+}
+
+// write the grad; SGD: v = mu*buf + g; buf = v; prm -= lr*v, exactly
+// like sgd_step_kernel (a null buffer means no momentum)
+template <bool SGD>
+__device__ __forceinline__ void net_gw_elem_close(const GwElem& e, float acc,
+                                                  float lr, float mu) {
+  *e.g = acc;
+  if (SGD) {
+    float v = acc;
+    if (e.buf) {
+      v = mu * e.b + acc;
+      *e.buf = v;
+    }
+    *e.prm = e.p - lr * v;
+  }
+}
+
+// sum the nblk_fwd per-block loss partials of the forward kernel into
+// loss_out (null loss_part: legacy mode, nothing to do)
+__device__ __forceinline__ void net_gw_loss_block(
+    const float* __restrict__ loss_part, float* __restrict__ loss_out,
+    int nblk_fwd, float* sh) {
+  const int tid = threadIdx.x;
+  if (loss_part) {  // block-uniform
+    float v = 0.f;
+    for (int base = 0; base < nblk_fwd; base += 4 * 256) {
+      float t[4];
+      #pragma unroll
+      for (int k = 0; k < 4; ++k)
+        t[k] = loss_part[min(base + k * 256 + tid, nblk_fwd - 1)];
+      #pragma unroll
+      for (int k = 0; k < 4; ++k)
+        v += (base + k * 256 + tid < nblk_fwd) ? t[k] : 0.f;
+    }
+    v = block_sum(v, sh);
+    if (tid == 0) *loss_out = v;
+  }
+}
+
+template <bool SGD>
+__device__ __forceinline__ void net_gw_combine_body(
+    const float* __restrict__ part, const GwPtrs& g, const GwPtrs& prm,
+    const GwPtrs& buf, int nch, int nch1, int nch2, float lr, float mu,
+    const float* __restrict__ loss_part, float* __restrict__ loss_out,
+    int nblk_fwd, unsigned long long* seed_bump) {
+  __shared__ float sh[NWAVE * 16];
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  if (blk == GW_CB_C1) {
+    net_gw_loss_block(loss_part, loss_out, nblk_fwd, sh);
+    return;
+  }
+  if (blk == GW_CB_C1 + 1) {
+    // advance the dropout seed for the NEXT step.  The convention is
+    // bump-AFTER everywhere: the step consumes the current seed, the
+    // combine advances it; a null pointer leaves it alone.
+    if (tid == 0 && seed_bump) *seed_bump += SEED_INC;
+    return;
+  }
+  if (blk < GW_CB_C1) {  // conv1: 16 elements x 16 row groups
+    const int el = tid & 15, r = tid >> 4;
+    const int i = min(blk * 16 + el, 259);
+    const bool live = tid < 16 && blk * 16 + el < 260;
+    const GwElem e = net_gw_elem_open<SGD, true>(i, g, prm, buf);
+    const int slot = r & 7;
+    const int col = slot == 0 ? i : GW_TOTAL + (slot - 1) * 260 + i;
+    float t[16];
+    #pragma unroll
+    for (int k = 0; k < 16; ++k)
+      t[k] = part[min(2 * k + (r >> 3), nch1 - 1) * GW_ROW + col];
+    #pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (2 * k + (r >> 3) >= nch1) t[k] = 0.f;
+    float acc = 0.f;
+    #pragma unroll
+    for (int k = 0; k < 16; k += 8) {
+      const float t8[8] = {t[k], t[k + 1], t[k + 2], t[k + 3],
+                           t[k + 4], t[k + 5], t[k + 6], t[k + 7]};
+      acc += tree8(t8);
+    }
+    acc += __shfl_xor(acc, 16, 64);  // the wave's 4 groups
+    acc += __shfl_xor(acc, 32, 64);
+    if ((tid & 63) < 16) sh[(tid >> 6) * 16 + el] = acc;
+    __syncthreads();
+    if (live)
+      net_gw_elem_close<SGD>(
+          e, (sh[el] + sh[16 + el]) + (sh[32 + el] + sh[48 + el]), lr, mu);
+    return;
+  }
+  // fc and conv2 regions: 4 lanes per element
+  const int t4 = (blk - GW_CB_C1 - 2) * 256 + tid;
+  const int q = t4 & 3;
+  const bool live = q == 0 && OFF_W2 + (t4 >> 2) < GW_TOTAL;
+  const int i = min(OFF_W2 + (t4 >> 2), GW_TOTAL - 1);
+  const GwElem e = net_gw_elem_open<SGD, false>(i, g, prm, buf);
+  const int n = i < OFF_WF1 ? nch2 : nch;
+  float t[GW_MAX_CH / 4];
+  #pragma unroll
+  for (int k = 0; k < GW_MAX_CH / 4; ++k)
+    t[k] = part[min(q + 4 * k, n - 1) * GW_ROW + i];
+  #pragma unroll
+  for (int k = 0; k < GW_MAX_CH / 4; ++k)
+    if (q + 4 * k >= n) t[k] = 0.f;
+  static_assert(GW_MAX_CH / 4 == 8, "the lane sum is one tree8");
+  float acc = tree8(t);
+  acc += __shfl_xor(acc, 1, 4);
+  acc += __shfl_xor(acc, 2, 4);
+  if (live) net_gw_elem_close<SGD>(e, acc, lr, mu);
+}
+
+// combine alone (the world>1 path: the all-reduce sits between it and
+// the optimizer step)
+__global__ void __launch_bounds__(256)
+net_gw_combine_kernel(const float* __restrict__ part, GwPtrs g, int nch,
+                      int nch1, int nch2,
+                      const float* __restrict__ loss_part,
+                      float* __restrict__ loss_out, int nblk_fwd,
+                      unsigned long long* seed_bump) {
+  net_gw_combine_body<false>(part, g, g, g, nch, nch1, nch2, 0.f, 0.f,
+                             loss_part, loss_out, nblk_fwd, seed_bump);
 }
 
 // combine + SGD in one dispatch (single-GPU training: there is no
 // gradient all-reduce between combine and the optimizer step, so the
-// ~4.5 us dispatch floor of the separate sgd_step_kernel is pure
-// overhead).  Writes the grad (so .grad stays inspectable), updates
-// the momentum buffer and the parameter exactly like sgd_step_kernel.
-__global__ void net_gw_combine_sgd_kernel(const float* __restrict__ part,
-                                          GwPtrs g, GwPtrs prm,
-                                          GwPtrs buf, int nch, int nch1,
-                                          int nch2,
-                                          float lr,
-                                          float mu,
-                                          const float* __restrict__ loss_part,
-                                          float* __restrict__ loss_out,
-                                          int nblk_fwd,
-                                          unsigned long long* seed_bump) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  for (int64_t t4 = blockIdx.x * blockDim.x + threadIdx.x;
-       t4 < (int64_t)GW_TOTAL * 4;
-       t4 += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(t4 >> 2), q = (int)(t4 & 3);
-    const float acc = net_gw_combine_elem_quad(i, q, nch, nch1, nch2,
-                                               part);
-    if (q == 0) {
-      const int t = net_gw_tensor_of(i, off);
-      const int64_t j = i - off[t];
-      g.p[t][j] = acc;
-      float v = acc;
-      if (buf.p[t]) {
-        v = mu * buf.p[t][j] + acc;
-        buf.p[t][j] = v;
-      }
-      prm.p[t][j] -= lr * v;
-    }
-  }
-  if ((loss_part || seed_bump) && blockIdx.x == 0)
-    net_loss_finalize(loss_part, loss_out, nblk_fwd, seed_bump);
+// dispatch of a separate sgd_step_kernel is pure overhead).  Writes the
+// grad (so .grad stays inspectable), updates the momentum buffer and
+// the parameter exactly like sgd_step_kernel.
+__global__ void __launch_bounds__(256)
+net_gw_combine_sgd_kernel(const float* __restrict__ part, GwPtrs g,
+                          GwPtrs prm, GwPtrs buf, int nch, int nch1,
+                          int nch2, float lr, float mu,
+                          const float* __restrict__ loss_part,
+                          float* __restrict__ loss_out, int nblk_fwd,
+                          unsigned long long* seed_bump) {
+  net_gw_combine_body<true>(part, g, prm, buf, nch, nch1, nch2, lr, mu,
+                            loss_part, loss_out, nblk_fwd, seed_bump);
 }
 
 // ---------------------------------------------------------------------------
@@ -1837,15 +1944,16 @@ static bool gw_fold_on() {
 //   nch  (fc1, fc2): 16 up to B=192 (B=128: 55.5 us vs 58.3 at 24, 61.7
 //        at 32), 24 above (B=512: 106.8 vs 110.3 us at 32; B=4096: 595
 //        vs 634 at the old uniform 32).
-//   nch1 (conv1) follows nch: its combine cost scales with nch1 * 7
-//        extension rows (B=128 55.2 us at 16 vs 58.1 at 24; B=1024 180.9
-//        at 24 vs 182.6 at 32).
+//   nch1 (conv1) follows nch.  That was settled while the combine
+//        folded the nch1 * 7 extension rows in a serial loop (B=128 55.2
+//        us at 16 vs 58.1 at 24); the combine no longer pays per row, and
+//        the re-sweep (profiles/gw_combine_numbers.md) has B=512 at 93.3
+//        us with 32 vs 95.3 at 24: a lead, not yet a default.
 //   nch2 (conv2), the family with the most arithmetic: 24 up to B=192
 //        (B=128 55.2 us vs 56.1 at 32, 56.9 at 16), above that the most
 //        rows the workspace holds (B=512 105.8 us at 32 vs 106.8 at 24).
 // The fold path keeps uniform chunks (its per-column tickets assume it).
 // gy is the partial kernel's gridDim.y.
-#define GW_MAX_CH 32  // rows of the part workspace
 struct GwPlan { int nch, nch1, nch2, bchunk, bchunk1, bchunk2, gy; };
 
 static GwPlan gw_plan(int B) {
@@ -2015,7 +2123,7 @@ static void launch_gw(const float* x, const NetWs& w, int B, GwPtrs gp,
                      dim3(256), 0, s, x, w.p1, w.p2, w.d3, w.ga1, w.ga2,
                      w.gh1, w.glog, w.part, B, pl.bchunk, pl.bchunk1,
                      pl.bchunk2, pl.nch, pl.nch1, pl.nch2, 0);
-  const dim3 grid((GW_TOTAL * 4 + 255) / 256);
+  const dim3 grid = net_gw_combine_grid();
   if (!sgd)
     hipLaunchKernelGGL(net_gw_combine_kernel, grid, dim3(256), 0, s,
                        (const float*)w.part, gp, pl.nch, pl.nch1, pl.nch2,
@@ -2119,6 +2227,14 @@ py::dict gw_plan_py(int B) {
   return d;
 }
 
+// the combine clamps its row index to [0, count - 1]
+static void check_gw_counts(int nch, int nch1, int nch2, const char* what) {
+  for (int n : {nch, nch1, nch2})
+    if (n < 1 || n > GW_MAX_CH)
+      throw std::invalid_argument(std::string(what) +
+                                  ": chunk counts must be in [1, 32]");
+}
+
 // raw combine launch (microbenchmarks: time the combine/sgd dispatch
 // in isolation)
 void net_gw_combine_raw(uintptr_t part_ws,
@@ -2126,8 +2242,9 @@ void net_gw_combine_raw(uintptr_t part_ws,
                         int nch1, int nch2,
                         uintptr_t stream) {
   const GwPtrs gp = gw_ptrs(grd_v, "net_gw_combine_raw grads");
+  check_gw_counts(nch, nch1, nch2, "net_gw_combine_raw");
   hipLaunchKernelGGL(net_gw_combine_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
+                     net_gw_combine_grid(), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, nch, nch1,
                      nch2, nullptr, nullptr, 0, nullptr);
 }
@@ -2144,8 +2261,9 @@ void net_gw_combine_sgd_raw(uintptr_t part_ws,
                             int nblk_fwd, uintptr_t stream) {
   const GwPtrs gp = gw_ptrs(grd_v, "net_gw_combine_sgd_raw grads");
   const GwPtrs pp = gw_ptrs(prm_v, "net_gw_combine_sgd_raw params");
+  check_gw_counts(nch, nch1, nch2, "net_gw_combine_sgd_raw");
   hipLaunchKernelGGL(net_gw_combine_sgd_kernel,
-                     dim3((GW_TOTAL * 4 + 255) / 256), dim3(256), 0,
+                     net_gw_combine_grid(), dim3(256), 0,
                      S(stream), (const float*)part_ws, gp, pp,
                      buf_ptrs(buf_v), nch,
                      nch1, nch2, (float)lr, (float)mu,
