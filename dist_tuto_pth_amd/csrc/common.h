@@ -1,6 +1,7 @@
 // common.h — what the HIP translation units of _kernels.so share:
 // error check, stream cast, grid sizing, the bf16 element type and its
 // conversions, the aligned vector access (Raw, Vec, load_vec, store_vec),
+// the vector-then-tail sweep built on it (vec_sweep),
 // the fixed-order sums (tree8, block_sum), the dispatch on dtype and access
 // width (by_dtype, by_dtype_width), the dropout RNG and the device-seed
 // advance.  One definition each, so the fp32, bf16 and fused-Net paths
@@ -88,6 +89,24 @@ __device__ __forceinline__ void store_vec(T* p, const float (&f)[V]) {
 #pragma unroll
   for (int j = 0; j < V; ++j) from_f(f[j], u.e[j]);
   *reinterpret_cast<typename Raw<sizeof(T) * V>::type*>(p) = u.raw;
+}
+
+// Grid-stride sweep over n elements of T, 16 bytes at a time and then a
+// scalar tail: calls f(i, integral_constant<int, V>) for the V elements
+// from i, with V = 16 / sizeof(T) in the body and V = 1 in the tail.  The
+// caller guarantees that whatever f reads or writes V-wide at i is aligned,
+// and launches BLK threads per block (blockDim.x read in a device function
+// costs a dependent load at the start of the kernel).
+template <typename T, class F>
+__device__ __forceinline__ void vec_sweep(int64_t n, F&& f) {
+  constexpr int V = 16 / sizeof(T);
+  const int64_t tid = (int64_t)blockIdx.x * BLK + threadIdx.x;
+  const int64_t nth = (int64_t)gridDim.x * BLK;
+  const int64_t nvec = n / V;
+  for (int64_t i = tid; i < nvec; i += nth)
+    f(i * V, std::integral_constant<int, V>{});
+  for (int64_t i = nvec * V + tid; i < n; i += nth)
+    f(i, std::integral_constant<int, 1>{});
 }
 
 // Fixed-order sums: the bits of every reduction built on them depend on

@@ -7,40 +7,63 @@
 // The reference gets these ops implicitly from torch
 // (Net.forward train_dist.py:64-71, SGD train_dist.py:110,124); here
 // each is an explicit HIP kernel designed for CDNA4: 64-wide wavefronts,
-// 256-thread blocks, vectorized float4 global access where layout
-// permits, LDS staging for the conv/linear operand reuse, grid-stride
+// 256-thread blocks, 16-byte global access where layout permits
+// (vec_sweep), LDS staging of the conv/linear weights, grid-stride
 // loops capped so the 256-CU chip is filled without launch spam.
 //
 // fp32 throughout (the reference trains fp32); bf16 enters for the
-// ring-allreduce reduction path (BASELINE config 5).
+// ring-allreduce reduction path (BASELINE config 5), as bf16_t with its
+// arithmetic in fp32 like every other bf16 path (common.h).
 // Build: hipcc --offload-arch=gfx950 (build.py).  No CUDA paths.
 //
-// This file also owns PYBIND11_MODULE; the pointwise ops (pointwise.hip),
-// the fused whole-Net step (net_fused.hip), the bf16 linear
-// (linear_bf16.hip), the bf16 convolution (conv_bf16.hip), batch
-// normalization (batchnorm.hip) and the general pooling ops (pool.hip)
-// register their bindings through register_pointwise() /
-// register_net_fused() / register_linear_bf16() / register_conv_bf16() /
-// register_batchnorm() / register_pool(); the cross-entropy loss
-// (cross_entropy.hip) through register_cross_entropy().
+// This file also owns PYBIND11_MODULE; each other translation unit
+// registers its bindings through the register_*() function declared in
+// front of the module.
 
 #include "common.h"
-
-#include <hip/hip_bf16.h>
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
 #include <vector>
 
+namespace {
+
+// ===========================================================================
+// Weight staging for conv2d and linear.  A weight tensor of at most 64 KB
+// is copied into the dynamic LDS buffer once per block and read from
+// there; a larger one is read from global memory, where it is L2-hot and
+// shared by every block.  stage_for() decides on the host and
+// stage_weights() acts on it in the kernel.
+// ===========================================================================
+struct Staging {
+  int staged;
+  int lds_bytes;
+};
+
+Staging stage_for(int64_t nfloats) {
+  const int64_t need = nfloats * sizeof(float);
+  if (need <= 64 * 1024) return {1, (int)need};  // LDS budget per block
+  return {0, 0};
+}
+
+// where to read the n floats of w from; every thread of the block calls it
+__device__ __forceinline__ const float* stage_weights(const float* w, int n,
+                                                      int staged) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (!staged) return w;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) smem[i] = w[i];
+  __syncthreads();
+  return smem;
+}
+
 // ===========================================================================
 // K1/K2 — direct convolution, stride 1, no padding (the only form Net
 // uses: 5x5 kernels, C in {1,10}, K in {10,20}, H<=28).
-// One block per batch element; the input plane (C*H*W <= 7.84 KB) and
-// the full weight tensor (K*C*25 <= 19.5 KB) are staged in LDS, then
-// the block's 256 threads sweep the K*OH*OW output points of that
-// element.  Every input value is read from HBM exactly once per batch
-// element regardless of K.
+// One thread per output element across the whole tensor, grid-stride:
+// that fills the 256-CU chip at any batch size (a block per batch element
+// left half the chip idle at B=128).  The weights come through
+// stage_weights(); x is read from global memory, tiny and L2-resident.
 // ===========================================================================
 __global__ void conv2d_fwd_kernel(const float* __restrict__ x,
                                   const float* __restrict__ w,
@@ -48,20 +71,9 @@ __global__ void conv2d_fwd_kernel(const float* __restrict__ x,
                                   float* __restrict__ out,
                                   int B, int C, int H, int W,
                                   int K, int R, int S_, int staged) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int OH = H - R + 1, OW = W - S_ + 1;
-  // weights through LDS when they fit; global (L2-hot) otherwise
-  const float* ws = w;
-  if (staged) {
-    const int wn = K * C * R * S_;
-    for (int i = threadIdx.x; i < wn; i += blockDim.x) smem[i] = w[i];
-    __syncthreads();
-    ws = smem;
-  }
+  const float* ws = stage_weights(w, K * C * R * S_, staged);
 
-  // one thread per output element across the whole tensor: fills the
-  // 256-CU chip at any batch size (the per-batch-block form left half
-  // the chip idle at B=128); x is tiny and L2-resident.
   const int64_t n_out = (int64_t)B * K * OH * OW;
   const int xn = C * H * W;
   const int on = K * OH * OW;
@@ -92,21 +104,15 @@ __global__ void conv2d_fwd_kernel(const float* __restrict__ x,
 }
 
 // backward dx: gx[b,c,h,w] = sum_k sum_{r,s} gy[b,k,h-r,w-s] * w[k,c,r,s]
-// (valid range only).  gy plane (K*OH*OW <= 5.76 KB) + weights in LDS.
+// (valid range only).  One thread per gx element, grid-stride; the weights
+// come through stage_weights(), gy is read from global memory.
 __global__ void conv2d_bwd_x_kernel(const float* __restrict__ gy,
                                     const float* __restrict__ w,
                                     float* __restrict__ gx,
                                     int B, int C, int H, int W,
                                     int K, int R, int S_, int staged) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int OH = H - R + 1, OW = W - S_ + 1;
-  const float* ws = w;
-  if (staged) {
-    const int wn = K * C * R * S_;
-    for (int i = threadIdx.x; i < wn; i += blockDim.x) smem[i] = w[i];
-    __syncthreads();
-    ws = smem;
-  }
+  const float* ws = stage_weights(w, K * C * R * S_, staged);
 
   const int64_t n_in = (int64_t)B * C * H * W;
   const int xn = C * H * W;
@@ -137,8 +143,10 @@ __global__ void conv2d_bwd_x_kernel(const float* __restrict__ gy,
   }
 }
 
-// backward dw/db: per-block (per batch element) partials accumulated in
-// LDS, then atomically added into gw/gb (gw zeroed by the caller).
+// backward dw/db on a grid of (weight tiles, batch chunks): a thread owns
+// one gw (or gb) element and sums its chunk's batch elements in a register.
+// With one chunk it stores the sum; with more it adds it atomically into
+// gw/gb, which split_batch() zeroed.
 __global__ void conv2d_bwd_w_kernel(const float* __restrict__ x,
                                     const float* __restrict__ gy,
                                     float* __restrict__ gw,
@@ -202,16 +210,7 @@ __global__ void linear_fwd_kernel(const float* __restrict__ x,
                                   float* __restrict__ out,
                                   int B, int K, int N, int fuse_relu,
                                   int staged) {
-  // weights staged through LDS when they fit (Net's fc shapes);
-  // read from global (L2-resident, shared by every block) otherwise
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const float* ws = w;
-  if (staged) {
-    const int wn = N * K;
-    for (int i = threadIdx.x; i < wn; i += blockDim.x) smem[i] = w[i];
-    __syncthreads();
-    ws = smem;
-  }
+  const float* ws = stage_weights(w, N * K, staged);
 
   const int64_t n_out = (int64_t)B * N;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -237,14 +236,7 @@ __global__ void linear_bwd_x_kernel(const float* __restrict__ gy,
                                     const float* __restrict__ w,
                                     float* __restrict__ gx,
                                     int B, int K, int N, int staged) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const float* ws = w;
-  if (staged) {
-    const int wn = N * K;
-    for (int i = threadIdx.x; i < wn; i += blockDim.x) smem[i] = w[i];
-    __syncthreads();
-    ws = smem;
-  }
+  const float* ws = stage_weights(w, N * K, staged);
 
   const int64_t n_out = (int64_t)B * K;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -309,20 +301,23 @@ __global__ void linear_bwd_w_kernel(const float* __restrict__ x,
 // N is tiny (10): one thread per row, serial max/sum over N — the
 // tensor is L2-resident at these sizes and the op is launch-bound.
 // ===========================================================================
+// one row: orow = xr - logsumexp(xr)
+__device__ __forceinline__ void log_softmax_row(const float* xr, float* orow,
+                                                int N) {
+  float m = xr[0];
+  for (int i = 1; i < N; ++i) m = fmaxf(m, xr[i]);
+  float s = 0.f;
+  for (int i = 0; i < N; ++i) s += __expf(xr[i] - m);
+  const float lse = m + __logf(s);
+  for (int i = 0; i < N; ++i) orow[i] = xr[i] - lse;
+}
+
 __global__ void log_softmax_fwd_kernel(const float* __restrict__ x,
                                        float* __restrict__ out,
                                        int B, int N) {
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B;
-       b += (int64_t)gridDim.x * blockDim.x) {
-    const float* xr = x + b * N;
-    float* orow = out + b * N;
-    float m = xr[0];
-    for (int i = 1; i < N; ++i) m = fmaxf(m, xr[i]);
-    float s = 0.f;
-    for (int i = 0; i < N; ++i) s += __expf(xr[i] - m);
-    const float lse = m + __logf(s);
-    for (int i = 0; i < N; ++i) orow[i] = xr[i] - lse;
-  }
+       b += (int64_t)gridDim.x * blockDim.x)
+    log_softmax_row(x + b * N, out + b * N, N);
 }
 
 // gx = gy - exp(out) * sum(gy)
@@ -341,21 +336,19 @@ __global__ void log_softmax_bwd_kernel(const float* __restrict__ gy,
   }
 }
 
-__global__ void nll_loss_fwd_kernel(const float* __restrict__ logp,
-                                    const int64_t* __restrict__ target,
-                                    float* __restrict__ loss, int B, int N) {
-  __shared__ float part[256];
+// The two loss kernels add their block's share of the mean into *loss
+// (zeroed by the launcher): block_sum needs the BLK threads they are
+// launched with.
+__global__ __launch_bounds__(BLK) void nll_loss_fwd_kernel(
+    const float* __restrict__ logp, const int64_t* __restrict__ target,
+    float* __restrict__ loss, int B, int N) {
+  __shared__ float sh[NWAVE];
   float acc = 0.f;
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B;
        b += (int64_t)gridDim.x * blockDim.x)
     acc -= logp[b * N + target[b]];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(loss, part[0] / B);
+  const float sum = block_sum(acc, sh);
+  if (threadIdx.x == 0) atomicAdd(loss, sum / B);
 }
 
 // gloss arrives as a DEVICE scalar pointer so the whole backward is
@@ -371,32 +364,19 @@ __global__ void nll_loss_bwd_kernel(const int64_t* __restrict__ target,
 }
 
 // fused: logp + mean NLL in one pass (K9+K10)
-__global__ void log_softmax_nll_fwd_kernel(const float* __restrict__ x,
-                                           const int64_t* __restrict__ tgt,
-                                           float* __restrict__ logp,
-                                           float* __restrict__ loss,
-                                           int B, int N) {
-  __shared__ float part[256];
+__global__ __launch_bounds__(BLK) void log_softmax_nll_fwd_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ tgt,
+    float* __restrict__ logp, float* __restrict__ loss, int B, int N) {
+  __shared__ float sh[NWAVE];
   float acc = 0.f;
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B;
        b += (int64_t)gridDim.x * blockDim.x) {
-    const float* xr = x + b * N;
     float* lr = logp + b * N;
-    float m = xr[0];
-    for (int i = 1; i < N; ++i) m = fmaxf(m, xr[i]);
-    float s = 0.f;
-    for (int i = 0; i < N; ++i) s += __expf(xr[i] - m);
-    const float lse = m + __logf(s);
-    for (int i = 0; i < N; ++i) lr[i] = xr[i] - lse;
+    log_softmax_row(x + b * N, lr, N);
     acc -= lr[tgt[b]];
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s2 = blockDim.x / 2; s2 > 0; s2 >>= 1) {
-    if (threadIdx.x < s2) part[threadIdx.x] += part[threadIdx.x + s2];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(loss, part[0] / B);
+  const float sum = block_sum(acc, sh);
+  if (threadIdx.x == 0) atomicAdd(loss, sum / B);
 }
 
 // gx = (exp(logp) - onehot) * gloss / B
@@ -475,257 +455,187 @@ __global__ void sgd_step_kernel(MtArgs a, float lr, float mu, float wd,
 // 4-cycle instruction reduces 4x16 = 64 elements = 16 elem/cycle/wave,
 // while plain VALU v_add_f32 reduces 64 elem/cycle/wave — the matrix
 // pipe wastes a 16x output replication on a rank-1 operand.  The op is
-// HBM-bandwidth-bound anyway (reads P*N floats once); the float4
+// HBM-bandwidth-bound anyway (reads P*N floats once); the 16-byte
 // grid-stride form below saturates that.  MFMA belongs to GEMM-shaped
 // work, which this framework's models reach through the register-
 // blocked conv kernels above (shapes are 5x5/latency-bound, below the
 // MFMA payoff threshold) and hipBLASLt/MIOpen for ResNet-50.
+//
+// Each kernel is one vec_sweep (common.h) over T = float or bf16_t: 16
+// bytes per lane, then a scalar tail, every sum and product in fp32 and
+// one rounding to T at the store.
 // ===========================================================================
-__global__ void add_inplace_f32_kernel(float* __restrict__ dst,
-                                       const float* __restrict__ src,
-                                       int64_t n) {
-  const int64_t n4 = n / 4;
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 a = d4[i], b = s4[i];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    d4[i] = a;
-  }
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] += src[i];
+
+// The store of the two reductions.  fp32 is store_vec.  bf16 rounds with
+// the compiler's fp32 -> bf16 conversion (to nearest even, one
+// v_cvt_pk_bf16_f32 per pair on gfx950) where store_vec's f2bf is five
+// integer operations per element: measured at 16M elements, f2bf put
+// add_inplace 5 % and reduce_columns 1 % outside the run-to-run range of the
+// kernels this replaces.  A NaN keeps the bits the hardware gives it.
+template <int V>
+__device__ __forceinline__ void store_sum(float* p, const float (&f)[V]) {
+  store_vec<float, V>(p, f);
+}
+template <int V>
+__device__ __forceinline__ void store_sum(bf16_t* p, const float (&f)[V]) {
+  Vec<bf16_t, V> u;
+#pragma unroll
+  for (int j = 0; j < V; ++j)
+    u.e[j] = __builtin_bit_cast(bf16_t, static_cast<__bf16>(f[j]));
+  *reinterpret_cast<typename Raw<sizeof(bf16_t) * V>::type*>(p) = u.raw;
 }
 
-__global__ void add_inplace_bf16_kernel(__hip_bfloat16* __restrict__ dst,
-                                        const __hip_bfloat16* __restrict__ src,
-                                        int64_t n) {
-  // 8 bf16 (16 B) per lane (G13): short4-shaped access via uint4
-  const int64_t n8 = n / 8;
-  uint4* d8 = reinterpret_cast<uint4*>(dst);
-  const uint4* s8 = reinterpret_cast<const uint4*>(src);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint4 a = d8[i], b = s8[i];
-    __hip_bfloat162* ah = reinterpret_cast<__hip_bfloat162*>(&a);
-    const __hip_bfloat162* bh = reinterpret_cast<const __hip_bfloat162*>(&b);
-    #pragma unroll
-    for (int k = 0; k < 4; ++k) ah[k] = __hadd2(ah[k], bh[k]);
-    d8[i] = a;
-  }
-  for (int64_t i = n8 * 8 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = __hadd(dst[i], src[i]);
+template <typename T>
+__global__ __launch_bounds__(BLK) void add_inplace_kernel(
+    T* __restrict__ dst, const T* __restrict__ src, int64_t n) {
+  vec_sweep<T>(n, [=](int64_t i, auto width) {
+    constexpr int V = decltype(width)::value;
+    float a[V], b[V];
+    load_vec<T, V>(dst + i, a);
+    load_vec<T, V>(src + i, b);
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] += b[j];
+    store_sum<V>(dst + i, a);
+  });
 }
 
 // column reduction for the full-mesh reduce-scatter (K14): after the
 // grouped p2p exchange, rank i holds P-1 peer chunks contiguously in
 // scratch; one kernel folds them all into the owned chunk.
-// dst[j] (+)= sum_p src[p*stride + j].  fp32 accumulates fp32; bf16
-// accumulates in fp32 and rounds ONCE at the end (better than serial
-// bf16 adds — BASELINE config 5 accuracy note, SURVEY.md §7 hard part d).
-__global__ void reduce_columns_f32_kernel(float* __restrict__ dst,
-                                          const float* __restrict__ src,
-                                          int P, int64_t stride,
-                                          int64_t n, float scale) {
-  const int64_t n4 = n / 4;
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  const int64_t stride4 = stride / 4;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 a = d4[i];
-    for (int p = 0; p < P; ++p) {
-      float4 b = s4[p * stride4 + i];
-      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
-    d4[i] = a;
-  }
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float a = dst[i];
-    for (int p = 0; p < P; ++p) a += src[p * stride + i];
-    dst[i] = a * scale;
-  }
-}
-
-__global__ void reduce_columns_bf16_kernel(
-    __hip_bfloat16* __restrict__ dst,
-    const __hip_bfloat16* __restrict__ src, int P, int64_t stride,
+// dst[j] = (dst[j] + sum_p src[p*stride + j]) * scale, summed in the order
+// dst, p = 0..P-1.  bf16 so accumulates in fp32 and rounds ONCE at the end
+// (better than serial bf16 adds — BASELINE config 5 accuracy note,
+// SURVEY.md §7 hard part d).  The launcher checks that stride keeps every
+// row's 16-byte accesses aligned.
+template <typename T>
+__global__ __launch_bounds__(BLK) void reduce_columns_kernel(
+    T* __restrict__ dst, const T* __restrict__ src, int P, int64_t stride,
     int64_t n, float scale) {
-  const int64_t n8 = n / 8;
-  uint4* d8 = reinterpret_cast<uint4*>(dst);
-  const uint4* s8 = reinterpret_cast<const uint4*>(src);
-  const int64_t stride8 = stride / 8;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint4 av = d8[i];
-    const __hip_bfloat162* ah = reinterpret_cast<__hip_bfloat162*>(&av);
-    float2 acc[4];
-    #pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = __bfloat1622float2(ah[k]);
+  vec_sweep<T>(n, [=](int64_t i, auto width) {
+    constexpr int V = decltype(width)::value;
+    float a[V], b[V];
+    load_vec<T, V>(dst + i, a);
     for (int p = 0; p < P; ++p) {
-      uint4 bv = s8[p * stride8 + i];
-      const __hip_bfloat162* bh =
-          reinterpret_cast<const __hip_bfloat162*>(&bv);
-      #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float2 b = __bfloat1622float2(bh[k]);
-        acc[k].x += b.x;
-        acc[k].y += b.y;
-      }
+      load_vec<T, V>(src + p * stride + i, b);
+#pragma unroll
+      for (int j = 0; j < V; ++j) a[j] += b[j];
     }
-    uint4 ov;
-    __hip_bfloat162* oh = reinterpret_cast<__hip_bfloat162*>(&ov);
-    #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      oh[k] = __float22bfloat162_rn(
-          make_float2(acc[k].x * scale, acc[k].y * scale));
-    d8[i] = ov;
-  }
-  for (int64_t i = n8 * 8 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float a = __bfloat162float(dst[i]);
-    for (int p = 0; p < P; ++p)
-      a += __bfloat162float(src[p * stride + i]);
-    dst[i] = __float2bfloat16(a * scale);
-  }
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] *= scale;
+    store_sum<V>(dst + i, a);
+  });
 }
 
-__global__ void scale_f32_kernel(float* __restrict__ dst, float s,
-                                 int64_t n) {
-  const int64_t n4 = n / 4;
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 a = d4[i];
-    a.x *= s; a.y *= s; a.z *= s; a.w *= s;
-    d4[i] = a;
-  }
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] *= s;
+__global__ __launch_bounds__(BLK) void scale_f32_kernel(
+    float* __restrict__ dst, float s, int64_t n) {
+  vec_sweep<float>(n, [=](int64_t i, auto width) {
+    constexpr int V = decltype(width)::value;
+    float a[V];
+    load_vec<float, V>(dst + i, a);
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] *= s;
+    store_vec<float, V>(dst + i, a);
+  });
 }
 
-// grid-throttled float4 copy: a stand-in for a link-bound transfer in
+// grid-throttled 16-byte copy: a stand-in for a link-bound transfer in
 // single-GPU overlap probes.  RCCL moves an xGMI peer copy with a few
 // workgroups at ~153 GB/s per link — a full-rate DtoD memcpy (5+ TB/s,
 // all of HBM) is the WRONG model for it.  Limiting the grid caps the
 // copy's HBM draw so the concurrent reduce kernel has headroom, which
 // is exactly the real pipeline's situation.
-__global__ void copy_throttled_f32_kernel(float* __restrict__ dst,
-                                          const float* __restrict__ src,
-                                          int64_t n) {
-  const int64_t n4 = n / 4;
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x)
-    d4[i] = s4[i];
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = src[i];
+__global__ __launch_bounds__(BLK) void copy_throttled_f32_kernel(
+    float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+  vec_sweep<float>(n, [=](int64_t i, auto width) {
+    constexpr int V = decltype(width)::value;
+    float v[V];
+    load_vec<float, V>(src + i, v);
+    store_vec<float, V>(dst + i, v);
+  });
 }
-
 
 // ===========================================================================
 // host launchers + pybind
 // ===========================================================================
-namespace {
 
 void conv2d_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
                 int B, int C, int H, int W, int K, int R, int S_,
                 uintptr_t stream) {
-  const int64_t need = (int64_t)K * C * R * S_ * sizeof(float);
-  const int staged = need <= 64 * 1024 ? 1 : 0;
+  const Staging st = stage_for((int64_t)K * C * R * S_);
   const int OH = H - R + 1, OW = W - S_ + 1;
   const int64_t n = (int64_t)B * K * OH * OW;
   hipLaunchKernelGGL(conv2d_fwd_kernel, dim3(grid_for(n, BLK)), dim3(BLK),
-                     staged ? (int)need : 0, S(stream), (const float*)x,
+                     st.lds_bytes, S(stream), (const float*)x,
                      (const float*)w, (const float*)bias, (float*)out, B,
-                     C, H, W, K, R, S_, staged);
+                     C, H, W, K, R, S_, st.staged);
+}
+
+// The weight-gradient kernels of conv2d and linear run on a grid of
+// (wtiles, nchunks): wn weights in tiles of BLK, the batch in chunks of
+// bchunk, halved until the grid has about 512 blocks.  More than one chunk
+// accumulates atomically, so gw[wn] and gb[nb] (if any) are zeroed first.
+struct BatchSplit {
+  int wtiles, bchunk, nchunks;
+};
+
+BatchSplit split_batch(int B, int wn, uintptr_t gw, uintptr_t gb, int nb,
+                       uintptr_t stream) {
+  BatchSplit s{(wn + BLK - 1) / BLK, B, 1};
+  while (s.bchunk > 1 && s.wtiles * ((B + s.bchunk - 1) / s.bchunk) < 512)
+    s.bchunk = (s.bchunk + 1) / 2;
+  s.nchunks = (B + s.bchunk - 1) / s.bchunk;
+  if (s.nchunks > 1) {
+    HIP_CHECK(hipMemsetAsync((void*)gw, 0, (size_t)wn * sizeof(float),
+                             S(stream)));
+    if (gb)
+      HIP_CHECK(hipMemsetAsync((void*)gb, 0, nb * sizeof(float),
+                               S(stream)));
+  }
+  return s;
 }
 
 void conv2d_bwd(uintptr_t x, uintptr_t w, uintptr_t gy, uintptr_t gx,
                 uintptr_t gw, uintptr_t gb, int B, int C, int H, int W,
                 int K, int R, int S_, uintptr_t stream) {
-  const int OH = H - R + 1, OW = W - S_ + 1;
-  {
-    const int64_t need = (int64_t)K * C * R * S_ * sizeof(float);
-    const int staged = need <= 64 * 1024 ? 1 : 0;
-    const int64_t n = (int64_t)B * C * H * W;
-    hipLaunchKernelGGL(conv2d_bwd_x_kernel, dim3(grid_for(n, BLK)),
-                       dim3(BLK), staged ? (int)need : 0, S(stream),
-                       (const float*)gy, (const float*)w, (float*)gx, B,
-                       C, H, W, K, R, S_, staged);
-  }
-  {
-    const int wn = K * C * R * S_;
-    // pick the batch chunk so the grid lands near ~512 blocks
-    int bchunk = B;
-    const int wtiles = (wn + BLK - 1) / BLK;
-    while (bchunk > 1 && wtiles * ((B + bchunk - 1) / bchunk) < 512)
-      bchunk = (bchunk + 1) / 2;
-    const int nchunks = (B + bchunk - 1) / bchunk;
-    if (nchunks > 1) {
-      HIP_CHECK(hipMemsetAsync((void*)gw, 0, (size_t)wn * sizeof(float),
-                               S(stream)));
-      if (gb)
-        HIP_CHECK(hipMemsetAsync((void*)gb, 0, K * sizeof(float),
-                                 S(stream)));
-    }
-    hipLaunchKernelGGL(conv2d_bwd_w_kernel, dim3(wtiles, nchunks),
-                       dim3(BLK), 0, S(stream), (const float*)x,
-                       (const float*)gy, (float*)gw, (float*)gb, B, C, H,
-                       W, K, R, S_, bchunk);
-  }
+  const int wn = K * C * R * S_;
+  const Staging st = stage_for(wn);
+  const int64_t n = (int64_t)B * C * H * W;
+  hipLaunchKernelGGL(conv2d_bwd_x_kernel, dim3(grid_for(n, BLK)), dim3(BLK),
+                     st.lds_bytes, S(stream), (const float*)gy,
+                     (const float*)w, (float*)gx, B, C, H, W, K, R, S_,
+                     st.staged);
+  const BatchSplit sp = split_batch(B, wn, gw, gb, K, stream);
+  hipLaunchKernelGGL(conv2d_bwd_w_kernel, dim3(sp.wtiles, sp.nchunks),
+                     dim3(BLK), 0, S(stream), (const float*)x,
+                     (const float*)gy, (float*)gw, (float*)gb, B, C, H, W,
+                     K, R, S_, sp.bchunk);
 }
 
 void linear_fwd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t out,
                 int B, int K, int N, bool fuse_relu, uintptr_t stream) {
-  const int64_t need = (int64_t)N * K * sizeof(float);
-  const int staged = need <= 64 * 1024 ? 1 : 0;  // LDS budget per WG
+  const Staging st = stage_for((int64_t)N * K);
   hipLaunchKernelGGL(linear_fwd_kernel,
                      dim3(grid_for((int64_t)B * N, BLK)), dim3(BLK),
-                     staged ? (int)need : 0,
-                     S(stream), (const float*)x, (const float*)w,
-                     (const float*)bias, (float*)out, B, K, N,
-                     fuse_relu ? 1 : 0, staged);
+                     st.lds_bytes, S(stream), (const float*)x,
+                     (const float*)w, (const float*)bias, (float*)out, B, K,
+                     N, fuse_relu ? 1 : 0, st.staged);
 }
 
 void linear_bwd(uintptr_t x, uintptr_t w, uintptr_t gy, uintptr_t out,
                 uintptr_t gx, uintptr_t gw, uintptr_t gb, int B, int K,
                 int N, uintptr_t stream) {
-  {
-    const int64_t need = (int64_t)N * K * sizeof(float);
-    const int staged = need <= 64 * 1024 ? 1 : 0;
-    hipLaunchKernelGGL(linear_bwd_x_kernel,
-                       dim3(grid_for((int64_t)B * K, BLK)), dim3(BLK),
-                       staged ? (int)need : 0,
-                       S(stream), (const float*)gy, (const float*)out,
-                       (const float*)w, (float*)gx, B, K, N, staged);
-  }
-  {
-    const int wn = N * K;
-    const int wtiles = (wn + BLK - 1) / BLK;
-    int bchunk = B;
-    while (bchunk > 1 && wtiles * ((B + bchunk - 1) / bchunk) < 512)
-      bchunk = (bchunk + 1) / 2;
-    const int nchunks = (B + bchunk - 1) / bchunk;
-    if (nchunks > 1) {
-      HIP_CHECK(hipMemsetAsync((void*)gw, 0, (size_t)wn * sizeof(float),
-                               S(stream)));
-      if (gb)
-        HIP_CHECK(hipMemsetAsync((void*)gb, 0, N * sizeof(float),
-                                 S(stream)));
-    }
-    hipLaunchKernelGGL(linear_bwd_w_kernel, dim3(wtiles, nchunks),
-                       dim3(BLK), 0, S(stream), (const float*)x,
-                       (const float*)gy, (const float*)out, (float*)gw,
-                       (float*)gb, B, K, N, bchunk);
-  }
+  const int wn = N * K;
+  const Staging st = stage_for(wn);
+  hipLaunchKernelGGL(linear_bwd_x_kernel,
+                     dim3(grid_for((int64_t)B * K, BLK)), dim3(BLK),
+                     st.lds_bytes, S(stream), (const float*)gy,
+                     (const float*)out, (const float*)w, (float*)gx, B, K,
+                     N, st.staged);
+  const BatchSplit sp = split_batch(B, wn, gw, gb, N, stream);
+  hipLaunchKernelGGL(linear_bwd_w_kernel, dim3(sp.wtiles, sp.nchunks),
+                     dim3(BLK), 0, S(stream), (const float*)x,
+                     (const float*)gy, (const float*)out, (float*)gw,
+                     (float*)gb, B, K, N, sp.bchunk);
 }
 
 void log_softmax_fwd(uintptr_t x, uintptr_t out, int B, int N,
@@ -826,22 +736,25 @@ void require_aligned16(const char* op, const char* name, uintptr_t p) {
                                 " must be 16-byte aligned");
 }
 
+// The dtype argument of add_inplace and reduce_columns is the dist
+// wrapper's _DTYPE code, NCCL's numbering: 7 is fp32 and 9 is bf16.
+bool dtype_is_bf16(const char* op, int dtype) {
+  if (dtype != 7 && dtype != 9)
+    throw std::runtime_error(std::string(op) + ": unsupported dtype");
+  return dtype == 9;
+}
+
 void add_inplace(uintptr_t dst, uintptr_t src, int64_t n, int dtype,
                  uintptr_t stream) {
   if (n < 0) throw std::invalid_argument("add_inplace: n must be >= 0");
   require_aligned16("add_inplace", "dst", dst);
   require_aligned16("add_inplace", "src", src);
-  if (dtype == 7) {  // ncclFloat32 numbering (dist wrapper's _DTYPE)
-    hipLaunchKernelGGL(add_inplace_f32_kernel, dim3(grid_for(n, BLK, 4)),
-                       dim3(BLK), 0, S(stream), (float*)dst,
-                       (const float*)src, n);
-  } else if (dtype == 9) {  // bf16
-    hipLaunchKernelGGL(add_inplace_bf16_kernel, dim3(grid_for(n, BLK, 8)),
-                       dim3(BLK), 0, S(stream), (__hip_bfloat16*)dst,
-                       (const __hip_bfloat16*)src, n);
-  } else {
-    throw std::runtime_error("add_inplace: unsupported dtype");
-  }
+  by_dtype(dtype_is_bf16("add_inplace", dtype), [&](auto* t) {
+    using T = elem_t<decltype(t)>;
+    constexpr int V = 16 / sizeof(T);
+    hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(grid_for(n, BLK, V)),
+                       dim3(BLK), 0, S(stream), (T*)dst, (const T*)src, n);
+  });
 }
 
 void reduce_columns(uintptr_t dst, uintptr_t src, int P, int64_t stride,
@@ -849,27 +762,20 @@ void reduce_columns(uintptr_t dst, uintptr_t src, int P, int64_t stride,
   if (n < 0 || P < 0)
     throw std::invalid_argument("reduce_columns: n and P must be >= 0");
   require_aligned16("reduce_columns", "dst", dst);
-  if (P > 0) {  // P == 0 only scales dst and never reads src
-    const int64_t vec = dtype == 7 ? 4 : 8;
-    if (stride < 0 || stride % vec != 0)
-      throw std::invalid_argument(
-          "reduce_columns: stride must be a multiple of " +
-          std::to_string(vec) + " elements, got " + std::to_string(stride));
-    require_aligned16("reduce_columns", "src", src);
-  }
-  if (dtype == 7) {
-    hipLaunchKernelGGL(reduce_columns_f32_kernel,
-                       dim3(grid_for(n, BLK, 4)), dim3(BLK), 0, S(stream),
-                       (float*)dst, (const float*)src, P, stride, n,
-                       (float)scale);
-  } else if (dtype == 9) {
-    hipLaunchKernelGGL(reduce_columns_bf16_kernel,
-                       dim3(grid_for(n, BLK, 8)), dim3(BLK), 0, S(stream),
-                       (__hip_bfloat16*)dst, (const __hip_bfloat16*)src, P,
+  by_dtype(dtype_is_bf16("reduce_columns", dtype), [&](auto* t) {
+    using T = elem_t<decltype(t)>;
+    constexpr int V = 16 / sizeof(T);
+    if (P > 0) {  // P == 0 only scales dst and never reads src
+      if (stride < 0 || stride % V != 0)
+        throw std::invalid_argument(
+            "reduce_columns: stride must be a multiple of " +
+            std::to_string(V) + " elements, got " + std::to_string(stride));
+      require_aligned16("reduce_columns", "src", src);
+    }
+    hipLaunchKernelGGL(reduce_columns_kernel<T>, dim3(grid_for(n, BLK, V)),
+                       dim3(BLK), 0, S(stream), (T*)dst, (const T*)src, P,
                        stride, n, (float)scale);
-  } else {
-    throw std::runtime_error("reduce_columns: unsupported dtype");
-  }
+  });
 }
 
 void scale_f32(uintptr_t dst, double s, int64_t n, uintptr_t stream) {

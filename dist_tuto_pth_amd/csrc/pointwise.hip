@@ -108,23 +108,16 @@ __global__ void maxpool2d_relu_bwd_kernel(const T* __restrict__ gy,
 // ===========================================================================
 // K4 — standalone ReLU (fp32 only, float4-vectorized)
 // ===========================================================================
-__global__ void relu_fwd_kernel(const float* __restrict__ x,
-                                float* __restrict__ out, int64_t n) {
-  const int64_t n4 = n / 4;
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  float4* o4 = reinterpret_cast<float4*>(out);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 v = x4[i];
-    v.x = v.x > 0.f ? v.x : 0.f;
-    v.y = v.y > 0.f ? v.y : 0.f;
-    v.z = v.z > 0.f ? v.z : 0.f;
-    v.w = v.w > 0.f ? v.w : 0.f;
-    o4[i] = v;
-  }
-  for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = x[i] > 0.f ? x[i] : 0.f;
+__global__ __launch_bounds__(BLK) void relu_fwd_kernel(
+    const float* __restrict__ x, float* __restrict__ out, int64_t n) {
+  vec_sweep<float>(n, [=](int64_t i, auto width) {
+    constexpr int V = decltype(width)::value;
+    float v[V];
+    load_vec<float, V>(x + i, v);
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
+    store_vec<float, V>(out + i, v);
+  });
 }
 
 __global__ void relu_bwd_kernel(const float* __restrict__ gy,

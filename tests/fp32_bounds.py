@@ -541,6 +541,18 @@ def _f32_scalar(s):
     return torch.tensor(s, dtype=torch.float32)
 
 
+def _round_once(acc, dtype):
+    """fp32 to ``dtype``, rounded once to nearest even; a NaN becomes the
+    quiet NaN 0x7fc0 in bf16, which is what the kernels store for the sum
+    of a default NaN (0x7fc0, ``float("nan")``) and anything.  torch's own
+    conversion on the CPU gives 0x7fc0 or 0xffff for it, depending on the
+    host's vector instructions, so the model does not leave it to torch."""
+    out = acc.to(dtype)
+    if dtype == torch.bfloat16:
+        out.view(torch.int16)[acc.isnan()] = 0x7FC0
+    return out
+
+
 def reduce_columns_model(dst, src, P, stride, n, scale):
     """``dst[j] = (dst[j] + sum_p src[p*stride + j]) * scale`` for j < n, in
     place on the 1-D tensors ``dst`` and ``src`` (fp32 or bf16): the sum
@@ -549,12 +561,12 @@ def reduce_columns_model(dst, src, P, stride, n, scale):
     acc = dst[:n].float()
     for p in range(P):
         acc = acc + src[p * stride:p * stride + n].float()
-    dst[:n] = (acc * _f32_scalar(scale)).to(dst.dtype)
+    dst[:n] = _round_once(acc * _f32_scalar(scale), dst.dtype)
 
 
 def add_inplace_model(dst, src, n):
     """``dst[j] += src[j]`` for j < n: one fp32 add, rounded once."""
-    dst[:n] = (dst[:n].float() + src[:n].float()).to(dst.dtype)
+    dst[:n] = _round_once(dst[:n].float() + src[:n].float(), dst.dtype)
 
 
 def scale_f32_model(dst, scale, n):
@@ -571,8 +583,10 @@ POINTWISE_N = [1, 7, 1029]
 
 def reduce_values(n, dtype, gen):
     """Magnitudes in [0.5, 4) with random signs: every fp32 sum of two such
-    bf16 values is exact, so a native bf16 add and an fp32 add that is
-    then rounded agree."""
+    bf16 values is exact.  The kernels add in fp32 and round once by
+    construction, so exact sums are no longer required of the inputs
+    (``rounding_case`` has the inexact ones); they are merely still
+    tested."""
     mag = 0.5 + 3.5 * torch.rand(n, generator=gen)
     sign = torch.randint(0, 2, (n,), generator=gen) * 2 - 1
     v = (mag * sign).to(dtype)
@@ -583,6 +597,36 @@ def reduce_values(n, dtype, gen):
 
 def reduce_stride(n):
     return (n + 7) // 8 * 8 + 64
+
+
+ROUNDING_N = 1029           # vectors and a tail
+ROUNDING_P = [1, 7]
+ROUNDING_NAN = (3, ROUNDING_N - 1)      # in a vector; in the tail
+
+
+@functools.lru_cache(maxsize=None)
+def rounding_case(P, scale=1.0):
+    """bf16 inputs with plain ``randn`` values, whose fp32 sums do not fit
+    bf16: the one rounding of the contract decides the stored bits, and a
+    bf16 add per term or a second rounding would show.  ``P = None`` is
+    ``add_inplace``, otherwise ``reduce_columns`` over P rows.  Two
+    destination columns are NaN, one through ``dst`` and one through
+    ``src``.  Returns (big, src, want, stride): the destination starts at
+    ``big[REDUCE_OFFSET]``, and ``want`` is the model's result for ``big``.
+    Computed once, shared and never modified."""
+    n, off = ROUNDING_N, REDUCE_OFFSET
+    stride = reduce_stride(n)
+    g = _gen(n, -1 if P is None else P, int(scale * 8))
+    big = torch.randn(off + n + off, generator=g).bfloat16()
+    src = torch.randn((P or 1) * stride, generator=g).bfloat16()
+    big[off + ROUNDING_NAN[0]] = float("nan")
+    src[((P or 1) - 1) * stride + ROUNDING_NAN[1]] = float("nan")
+    want = big.clone()
+    if P is None:
+        add_inplace_model(want[off:], src, n)
+    else:
+        reduce_columns_model(want[off:], src, P, stride, n, scale)
+    return big, src, want, stride
 
 
 # ---------------------------------------------------------------------------

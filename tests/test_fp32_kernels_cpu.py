@@ -85,6 +85,42 @@ def test_reduction_contract_model():
     assert torch.equal(f, torch.tensor([0.25, 0.5, 3.0]))
 
 
+def _bf16_bits_once(f):
+    """fp32 -> bf16 bits in integer arithmetic: round to nearest even, any
+    NaN to 0x7fc0 (what the kernels' store conversion does)."""
+    u = f.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    r = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    r = torch.where((u & 0x7FFFFFFF) > 0x7F800000,
+                    torch.full_like(r, 0x7FC0), r)
+    return (r & 0xFFFF).to(torch.int32)
+
+
+@pytest.mark.parametrize("P", [None] + fb.ROUNDING_P)
+def test_reduction_contract_rounds_once(P):
+    """The expectation the GPU tests hold the bf16 kernels to at inexact
+    sums: the model's bits are the fp32 sum in the order dst, p = 0..P-1,
+    scaled, rounded once; the case has sums that need the rounding, and its
+    NaN columns come out as 0x7fc0."""
+    n, off = fb.ROUNDING_N, fb.REDUCE_OFFSET
+    for scale in ([1.0] if P is None else fb.REDUCE_SCALES):
+        big, src, want, stride = fb.rounding_case(P, scale)
+        acc = big[off:off + n].float()
+        for p in range(P or 1):
+            acc = acc + src[p * stride:p * stride + n].float()
+        acc = acc * torch.tensor(scale, dtype=torch.float32)
+        got = want.view(torch.int16).to(torch.int32) & 0xFFFF
+        assert torch.equal(got[off:off + n], _bf16_bits_once(acc))
+        # guards untouched; NaN where it went in; rounding had work to do
+        raw = big.view(torch.int16).to(torch.int32) & 0xFFFF
+        assert torch.equal(got[:off], raw[:off])
+        assert torch.equal(got[off + n:], raw[off + n:])
+        for j in fb.ROUNDING_NAN:
+            assert int(got[off + j]) == 0x7FC0
+        inexact = torch.isfinite(acc) & (acc.bfloat16().float() != acc)
+        print(f"P={P} scale={scale}: {int(inexact.sum())} of {n} inexact")
+        assert int(inexact.sum()) > n // 4
+
+
 def test_pad_chunks_realigns_a_misaligned_view():
     """The reduction launchers refuse a pointer off a 16-byte boundary, so
     the all-reduce algorithms route such a tensor through their aligned

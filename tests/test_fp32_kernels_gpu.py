@@ -159,6 +159,16 @@ def test_reduce_columns_matches_contract(dtype, P):
                              fb.NCCL_DTYPE[dtype], _stream())
             assert _bits_equal(bd.cpu(), want), (n, scale)
             assert _bits_equal(sd.cpu(), src)
+    if dtype == torch.bfloat16 and P in fb.ROUNDING_P:
+        # inexact sums and NaN: the one rounding decides the stored bits
+        for scale in fb.REDUCE_SCALES:
+            big, src, want, stride = fb.rounding_case(P, scale)
+            bd, sd = big.to(DEV), src.to(DEV)
+            k.reduce_columns(bd.data_ptr() + off * esz, sd.data_ptr(), P,
+                             stride, fb.ROUNDING_N, scale,
+                             fb.NCCL_DTYPE[dtype], _stream())
+            assert _bits_equal(bd.cpu(), want), scale
+            assert _bits_equal(sd.cpu(), src)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -176,6 +186,14 @@ def test_add_inplace_matches_contract(dtype):
         k.add_inplace(dd.data_ptr(), sd.data_ptr(), n,
                       fb.NCCL_DTYPE[dtype], _stream())
         assert _bits_equal(dd.cpu(), want), n
+        assert _bits_equal(sd.cpu(), src)
+    if dtype == torch.bfloat16:
+        # inexact sums and NaN: the one rounding decides the stored bits
+        big, src, want, _ = fb.rounding_case(None)
+        bd, sd = big.to(DEV), src.to(DEV)
+        k.add_inplace(bd.data_ptr() + fb.REDUCE_OFFSET * 2, sd.data_ptr(),
+                      fb.ROUNDING_N, fb.NCCL_DTYPE[dtype], _stream())
+        assert _bits_equal(bd.cpu(), want)
         assert _bits_equal(sd.cpu(), src)
 
 
