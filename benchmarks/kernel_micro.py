@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel microbenchmark of the fused ConvNet training step
 (hipEvent timing, 1 GPU).  Pinpoints where the step's microseconds go:
-fwd, data-bwd (bundled with gw, and alone: both kernels at each
-sibling-split), the four weight-gradient tile
+fwd (with its prologue, and alone: both kernels with one and two
+workgroups per sample), data-bwd (bundled with gw, and alone: both
+kernels at each sibling-split), the four weight-gradient tile
 segments separately, combine, sgd, prologue.
 
 Run on a GPU box:  python benchmarks/kernel_micro.py [--batch 128]
@@ -91,6 +92,20 @@ def main():
 
     results = {}
     results["fwd"] = time_fn(fwd)
+
+    # the forward alone (loss_part mode, no prologue dispatch): the tiled
+    # kernel and the 256-thread one, one and two workgroups per sample
+    def fwd_raw(tiled, split):
+        return lambda: k.net_fwd_raw(
+            x.data_ptr(), pp, tgt.data_ptr(), ws.ptrs, _seed_ptr(dev), B,
+            True, tiled, split, 60000, s)
+
+    for tiled in (True, False):
+        for sp in (1, 2):
+            if sp == 2 and B > 2048:
+                continue
+            name = "tiled" if tiled else "old"
+            results[f"fwd {name} (split={sp})"] = time_fn(fwd_raw(tiled, sp))
     # full bwd+gw+combine bundle is what bwd() launches; time the pieces
     for sp in (1, 2, 4, 8):
         os.environ["DTP_BWD_SPLIT"] = str(sp)

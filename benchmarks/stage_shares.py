@@ -82,11 +82,19 @@ def main():
         k.stage_stamps_clear()
         net_fused_step(net, x, tgt)
         st = torch.tensor(k.stage_stamps(), dtype=torch.int64).view(-1, n)
-        if tiled == "1":
-            shares(st, 9, FWD, f"forward, B={B}")
         shares(st, 0, BWD, f"data backward, B={B}, "
                + ("tiled kernel" if tiled == "1" else "strip kernel"))
     os.environ.pop("DTP_BWD_TILED", None)
+    for tiled in ("1", "0"):
+        os.environ["DTP_FWD_TILED"] = tiled
+        for _ in range(20):
+            net_fused_step(net, x, tgt)
+        k.stage_stamps_clear()
+        net_fused_step(net, x, tgt)
+        st = torch.tensor(k.stage_stamps(), dtype=torch.int64).view(-1, n)
+        shares(st, 9, FWD, f"forward, B={B}, "
+               + ("tiled kernel" if tiled == "1" else "256-thread kernel"))
+    os.environ.pop("DTP_FWD_TILED", None)
 
 
 if __name__ == "__main__":

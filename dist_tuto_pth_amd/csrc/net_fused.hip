@@ -165,7 +165,12 @@ __device__ __forceinline__ float gw_ld(const float* p) {
 // workgroup, activations staged through caller-provided LDS buffers.
 // Returns -— on tid 0 only — the sample's log-prob at the target
 // (callers accumulate the NLL loss); other lanes return 0.
-// Shared by net_fused_fwd_kernel and the single-launch net_step_kernel.
+// Shared by net_fused_fwdbwd_kernel, the single-launch net_step_kernel
+// and the two 256-thread forward kernels below it, which net_fused_fwd
+// runs only with DTP_FWD_TILED=0: its default is the re-blocked
+// net_fused_fwd_tiled_kernel further down (same arguments, workspace,
+// index bytes, dropout masks and hand-off; conv2's summation order
+// differs).
 // SPLIT mode (fused fwd at small B): TWO sibling workgroups per sample
 // fill the otherwise half-idle chip (B=128 launches 128 blocks on 256
 // CUs).  Both stage x/w1 and compute conv1+pool1 fully (duplicating
@@ -530,6 +535,422 @@ net_fused_fwd_split_kernel(
     const float lsum = half == 0 ? -lp_t / B : 0.f;
     if (loss_part) loss_part[blockIdx.x] = lsum;
     else if (half == 0) atomicAdd(loss, lsum);
+  }
+}
+
+// The re-blocked forward (net_fused_fwd's default up to B=256, see
+// fwd_tiled(); DTP_FWD_TILED=0 selects the two kernels above).  Same
+// arguments, workspace and semantics, same sibling hand-off, 512
+// threads, and the two conv stages
+// in the shape of the tiled data backward: an item holds a 2x8 block of
+// conv outputs in 16 accumulators and feeds 400 FMAs from 25 aligned
+// 16-byte LDS reads (a 6-row x 12-column window as 18 float4, a filter
+// padded to 28 floats as 7), where net_fwd_sample issues ~61 dword reads
+// per 100 FMAs at one wave per SIMD.
+//  - conv1 + pool1: item = (channel c, pooled row, group of 4 pooled
+//    columns), 360 items in one round, c the fastest lane index.  The
+//    accumulators start at the bias and run the taps in row-major order.
+//  - conv2: item = (output channel k, pooled row, group g of CPG input
+//    channels), 400 items either way: 10 k x 4 rows x 10 single channels
+//    for a sibling, 20 k x 4 rows x 5 channel pairs unsplit.  Every
+//    channel's 25 taps are summed from zero; a pair item adds its two
+//    channel sums.  The partials go through LDS and one thread per pooled
+//    cell adds them in ONE fixed order for both modes and the fallback,
+//    ((((s01 + s23) + s45) + s67) + s89) + bias with s_ab = s_a + s_b,
+//    then applies dropout, the 2x2 max, ReLU and the index byte.  So the
+//    split and unsplit kernels, and the hand-off's fallback, give the
+//    same bits.
+//  - LDS strides (brute-force scan of the item -> lane maps against the
+//    ds_read_b128 lane groups, profiles/convnet_step_history.md): filter
+//    stride 28 with the (k, c) slot as the lane index, p1 plane stride
+//    148 (37 quads, odd: ten channels land on ten bank quads; the
+//    natural 144 puts all of them on the same four).
+//  - fc1: 8 lanes per output on 400 lanes, ten float4 of wf1 per lane.
+#define FT_NT 512    // threads
+#define FT_WS 28     // staged filter stride
+#define FT_PS 148    // p1 plane stride
+#define FT_NITEM 400 // conv2 items
+static_assert(FT_WS % 4 == 0 && FT_PS % 4 == 0 && FT_PS >= 144 &&
+              FT_NITEM / 4 <= 128 && FT_NT == 4 * 128,
+              "aligned float4 reads; a pooled row's items on 128 lanes");
+
+// one input channel's 2x8 conv outputs: window rows 0..5 x 12 columns at
+// xw (row r = float4 3r .. 3r+2 when RS4 == 3), filter at wk
+template <int RS4>
+__device__ __forceinline__ void ft_conv_2x8(const float4* xw,
+                                            const float4* wk, float* q) {
+  float xv[6][12], wv[28];
+  #pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    #pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float4 t = xw[r * RS4 + j];
+      xv[r][4 * j] = t.x; xv[r][4 * j + 1] = t.y;
+      xv[r][4 * j + 2] = t.z; xv[r][4 * j + 3] = t.w;
+    }
+  }
+  #pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    const float4 t = wk[j];
+    wv[4 * j] = t.x; wv[4 * j + 1] = t.y;
+    wv[4 * j + 2] = t.z; wv[4 * j + 3] = t.w;
+  }
+  #pragma unroll
+  for (int r = 0; r < 5; ++r) {
+    #pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      #pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        #pragma unroll
+        for (int jj = 0; jj < 8; ++jj)
+          q[a * 8 + jj] = fmaf(xv[a + r][jj + s], wv[r * 5 + s],
+                               q[a * 8 + jj]);
+      }
+    }
+  }
+}
+
+// 2x2 max (first maximum wins) + ReLU of one pooled cell; returns the
+// index byte: window slot, bit 2 set when the ReLU is dead
+__device__ __forceinline__ uint8_t ft_pool(float q00, float q01, float q10,
+                                           float q11, float& o) {
+  int am = 0; float m = q00;
+  if (q01 > m) { m = q01; am = 1; }
+  if (q10 > m) { m = q10; am = 2; }
+  if (q11 > m) { m = q11; am = 3; }
+  o = m > 0.f ? m : 0.f;
+  return (uint8_t)(m > 0.f ? am : (am | 4));
+}
+
+template <bool SPLIT>
+__global__ void
+__launch_bounds__(FT_NT)
+net_fused_fwd_tiled_kernel(
+    const float* __restrict__ x,
+    const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2,
+    const float* __restrict__ wf1, const float* __restrict__ bf1,
+    const float* __restrict__ wf2, const float* __restrict__ bf2,
+    const int64_t* __restrict__ tgt,
+    float* __restrict__ p1_ws, uint8_t* __restrict__ idx1_ws,
+    uint8_t* __restrict__ m2_ws, float* __restrict__ p2_ws,
+    uint8_t* __restrict__ idx2_ws, float* __restrict__ h1_ws,
+    uint8_t* __restrict__ m3_ws, float* __restrict__ d3_ws,
+    float* __restrict__ logp_ws, float* __restrict__ loss,
+    float* __restrict__ loss_part,
+    const unsigned long long* __restrict__ seed_p,
+    int B, int training, unsigned int* __restrict__ flags,
+    unsigned int token, int poll_bound) {
+  constexpr int KL = SPLIT ? N_C2K / 2 : N_C2K;  // conv2 channels here
+  constexpr int NG = SPLIT ? 10 : 5;             // input-channel groups
+  constexpr int CPG = N_C1K / NG;                // channels per group
+  static_assert(4 * KL * NG == FT_NITEM, "conv2 items");
+  __shared__ __attribute__((aligned(16))) float xs[784];
+  __shared__ __attribute__((aligned(16))) float w1p[N_C1K * FT_WS];
+  __shared__ __attribute__((aligned(16))) float p1[N_C1K * FT_PS];
+  __shared__ __attribute__((aligned(16))) float w2p[KL * N_C1K * FT_WS];
+  __shared__ __attribute__((aligned(16))) float part[FT_NITEM * 16];
+  __shared__ __attribute__((aligned(16))) float p2[N_P2];
+  __shared__ float b1s[N_C1K];
+  __shared__ float b2s[KL];
+  __shared__ float d3[N_H1];
+  __shared__ float logits[N_CLS];
+  __shared__ unsigned s_got;
+  const int tid = threadIdx.x;
+  const uint64_t seed = seed_p[0];
+  // split: blockIdx = 2b + half, the grid is exactly 2B
+  const int half = SPLIT ? (blockIdx.x & 1) : 0;
+  const int k0 = half * KL;
+
+  STAGE_STAMP(9);
+  // the weights are staged once per workgroup: w1 as [c][28], w2 as
+  // [cc][k][g][28] for channel c = CPG*g + cc, so that consecutive
+  // conv2 lanes (g fastest, then k) read consecutive 28-float slots
+  for (int i = tid; i < N_C1K * 25; i += FT_NT) {
+    const int c = i / 25, j = i - c * 25;
+    w1p[c * FT_WS + j] = w1[i];
+  }
+  for (int i = tid; i < KL * N_C1K * 25; i += FT_NT) {
+    const int kc = i / 25, j = i - kc * 25;
+    const int kl = kc / N_C1K, c = kc - kl * N_C1K;
+    const int slot = ((c % CPG) * KL + kl) * NG + c / CPG;
+    w2p[slot * FT_WS + j] = w2[k0 * 250 + i];
+  }
+  if (tid < N_C1K) b1s[tid] = b1[tid];
+  if (tid < KL) b2s[tid] = b2[k0 + tid];
+
+  float lsum = 0.f;
+  for (int b = SPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x; b < B;
+       b += SPLIT ? B : (int)gridDim.x) {
+    if (tid < 196)
+      reinterpret_cast<float4*>(xs)[tid] =
+          reinterpret_cast<const float4*>(x + (int64_t)b * 784)[tid];
+    __syncthreads();
+    STAGE_STAMP(10);
+
+    // conv1 + pool1 + relu
+    if (tid < 360) {
+      const int c = tid % N_C1K, pg = tid / N_C1K;
+      const int ph = pg / 3, g = pg - ph * 3;
+      const float bias = b1s[c];
+      float q[16];
+      #pragma unroll
+      for (int j = 0; j < 16; ++j) q[j] = bias;
+      ft_conv_2x8<7>(
+          reinterpret_cast<const float4*>(xs + ph * 2 * 28 + g * 8),
+          reinterpret_cast<const float4*>(w1p + c * FT_WS), q);
+      float o[4];
+      uchar4 ib;
+      ib.x = ft_pool(q[0], q[1], q[8], q[9], o[0]);
+      ib.y = ft_pool(q[2], q[3], q[10], q[11], o[1]);
+      ib.z = ft_pool(q[4], q[5], q[12], q[13], o[2]);
+      ib.w = ft_pool(q[6], q[7], q[14], q[15], o[3]);
+      const float4 o4 = make_float4(o[0], o[1], o[2], o[3]);
+      const int cell = c * 144 + ph * 12 + g * 4;
+      *reinterpret_cast<float4*>(p1 + c * FT_PS + ph * 12 + g * 4) = o4;
+      if (!SPLIT || half == 0) {
+        *reinterpret_cast<float4*>(p1_ws + (int64_t)b * N_P1 + cell) = o4;
+        *reinterpret_cast<uchar4*>(idx1_ws + (int64_t)b * N_P1 + cell) = ib;
+      }
+    }
+    __syncthreads();
+    STAGE_STAMP(11);
+
+    // conv2: per-group partial sums of a 2x8 output block
+    // (a pooled row's 100 items sit on 128 lanes of their own: no wave
+    // mixes two rows, which is what the bank scan assumes)
+    if ((tid & 127) < NG * KL) {
+      const int ph = tid >> 7, it = tid & 127;
+      const int g = it % NG, kl = it / NG;
+      const int item = ph * (NG * KL) + it;
+      float q[16];
+      #pragma unroll
+      for (int cc = 0; cc < CPG; ++cc) {
+        float t[16];
+        #pragma unroll
+        for (int j = 0; j < 16; ++j) t[j] = 0.f;
+        ft_conv_2x8<3>(
+            reinterpret_cast<const float4*>(p1 + (g * CPG + cc) * FT_PS +
+                                            ph * 24),
+            reinterpret_cast<const float4*>(
+                w2p + ((cc * KL + kl) * NG + g) * FT_WS), t);
+        #pragma unroll
+        for (int j = 0; j < 16; ++j) q[j] = cc == 0 ? t[j] : q[j] + t[j];
+      }
+      // part[j][item]: consecutive lanes store consecutive float4
+      #pragma unroll
+      for (int j = 0; j < 4; ++j)
+        reinterpret_cast<float4*>(part)[j * FT_NITEM + item] =
+            make_float4(q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]);
+    }
+    __syncthreads();
+    // fixed-order sum of the partials + bias, dropout2d, pool2 + relu
+    if (tid < KL * 16) {
+      const int kl = tid >> 4, ph = (tid >> 2) & 3, pw = tid & 3;
+      const int k = k0 + kl;
+      float v[4];
+      #pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const float* pp = part + ((a * 2 + (pw >> 1)) * FT_NITEM +
+                                  ph * (NG * KL) + kl * NG) * 4 + (pw & 1) * 2;
+        float2 s = make_float2(0.f, 0.f);
+        #pragma unroll
+        for (int m = 0; m < 5; ++m) {
+          // group g's partial is 4 floats on from group g - 1's
+          float2 t = *reinterpret_cast<const float2*>(pp + m * (2 / CPG) * 4);
+          if (CPG == 1) {  // single channels: pair them first
+            const float2 u =
+                *reinterpret_cast<const float2*>(pp + (m * 2 + 1) * 4);
+            t.x += u.x; t.y += u.y;
+          }
+          s.x = m == 0 ? t.x : s.x + t.x;
+          s.y = m == 0 ? t.y : s.y + t.y;
+        }
+        v[a * 2] = s.x + b2s[kl];
+        v[a * 2 + 1] = s.y + b2s[kl];
+      }
+      if (training) {
+        const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + k);
+        const float dsc = (rr >= 0x80000000u) ? 2.f : 0.f;
+        v[0] *= dsc; v[1] *= dsc; v[2] *= dsc; v[3] *= dsc;
+      }
+      float o;
+      const uint8_t ib = ft_pool(v[0], v[1], v[2], v[3], o);
+      const int i = k0 * 16 + tid;
+      p2[i] = o;
+      gw_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
+      idx2_ws[(int64_t)b * N_P2 + i] = ib;
+    }
+    if ((!SPLIT || half == 0) && training && tid < N_C2K) {
+      const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + tid);
+      m2_ws[(int64_t)b * N_C2K + tid] = rr >= 0x80000000u;
+    }
+    __syncthreads();
+    STAGE_STAMP(12);
+
+    // the sibling hand-off: net_fwd_sample's protocol, unchanged
+    if (SPLIT && half == 1) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid == 0) {
+        __hip_atomic_store(flags + b, token, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        if (loss_part) loss_part[blockIdx.x] = 0.f;
+      }
+      return;  // fc/softmax belong to sibling 0
+    }
+    if (SPLIT) {
+      if (tid == 0) {
+        unsigned got = 0;
+        for (int it = 0; it < poll_bound; ++it) {
+          if (__hip_atomic_load(flags + b, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT) == token) {
+            got = 1u;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(4);
+        }
+        if (got)  // consume, so a graph replay waits for a fresh publish
+          __hip_atomic_store(flags + b, 0u, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+        s_got = got;
+      }
+      __syncthreads();
+      if (s_got) {
+        if (tid < N_P2 / 2)
+          p2[N_P2 / 2 + tid] =
+              gw_ld<true>(p2_ws + (int64_t)b * N_P2 + N_P2 / 2 + tid);
+      } else if (tid < N_P2 / 2) {
+        // the sibling is not resident yet: its channels from our own p1
+        // and w2 in global memory, one pooled cell per thread (cold, so
+        // at the old blocking), in the summation order of the items
+        const int i = N_P2 / 2 + tid;
+        const int k = i >> 4, ph = (i >> 2) & 3, pw = i & 3;
+        float v[4];
+        #pragma unroll 1
+        for (int m = 0; m < 5; ++m) {
+          float s[2][4];
+          #pragma unroll
+          for (int cc = 0; cc < 2; ++cc) {
+            const int c = 2 * m + cc;
+            const float* pp = p1 + c * FT_PS + ph * 24 + pw * 2;
+            const float* wc = w2 + (k * N_C1K + c) * 25;
+            float* t = s[cc];
+            t[0] = t[1] = t[2] = t[3] = 0.f;
+            #pragma unroll
+            for (int r = 0; r < 5; ++r) {
+              #pragma unroll
+              for (int ss = 0; ss < 5; ++ss) {
+                const float w = wc[r * 5 + ss];
+                const float* pr = pp + r * 12 + ss;
+                t[0] = fmaf(pr[0], w, t[0]);
+                t[1] = fmaf(pr[1], w, t[1]);
+                t[2] = fmaf(pr[12], w, t[2]);
+                t[3] = fmaf(pr[13], w, t[3]);
+              }
+            }
+          }
+          #pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float sp = s[0][j] + s[1][j];
+            v[j] = m == 0 ? sp : v[j] + sp;
+          }
+        }
+        const float bias = b2[k];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] += bias;
+        if (training) {
+          const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + k);
+          const float dsc = (rr >= 0x80000000u) ? 2.f : 0.f;
+          v[0] *= dsc; v[1] *= dsc; v[2] *= dsc; v[3] *= dsc;
+        }
+        float o;
+        ft_pool(v[0], v[1], v[2], v[3], o);
+        p2[i] = o;
+      }
+      __syncthreads();
+    }
+    STAGE_STAMP(13);
+
+    // fc1 (320->50) + relu + dropout: 8 lanes per output, shfl reduce.
+    // The pointer is opaque per sample so that the ten wf1 loads are not
+    // hoisted out of the sample loop (registers).
+    if (tid < N_H1 * 8) {
+      const int n = tid >> 3, q8 = tid & 7;
+      const float* wf1_b = wf1;
+      asm volatile("" : "+s"(wf1_b));
+      const float4* wr =
+          reinterpret_cast<const float4*>(wf1_b + n * N_P2 + q8 * 40);
+      const float4* pr = reinterpret_cast<const float4*>(p2 + q8 * 40);
+      float4 wv[10];
+      #pragma unroll
+      for (int j = 0; j < 10; ++j) wv[j] = wr[j];
+      float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
+      #pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        const float4 pv = pr[j];
+        e0 = fmaf(pv.x, wv[j].x, e0);
+        e1 = fmaf(pv.y, wv[j].y, e1);
+        e2 = fmaf(pv.z, wv[j].z, e2);
+        e3 = fmaf(pv.w, wv[j].w, e3);
+      }
+      float acc = (e0 + e1) + (e2 + e3);
+      acc += __shfl_down(acc, 1, 8);
+      acc += __shfl_down(acc, 2, 8);
+      acc += __shfl_down(acc, 4, 8);
+      if (q8 == 0) {
+        float h = acc + bf1[n];
+        h = h > 0.f ? h : 0.f;
+        h1_ws[(int64_t)b * N_H1 + n] = h;
+        float dd = h;
+        uint8_t keep = 1;
+        if (training) {
+          const uint32_t rr = mix32(seed ^ 0x5bd1e995u,
+                                    (uint64_t)b * N_H1 + n);
+          keep = rr >= 0x80000000u;
+          dd = keep ? h * 2.f : 0.f;
+        }
+        m3_ws[(int64_t)b * N_H1 + n] = keep;
+        d3_ws[(int64_t)b * N_H1 + n] = dd;
+        d3[n] = dd;
+      }
+    }
+    __syncthreads();
+    STAGE_STAMP(14);
+
+    // fc2 (50->10), then log_softmax + NLL on one lane, as net_fwd_sample
+    if (tid < N_CLS) {
+      const float* wr = wf2 + tid * N_H1;
+      float acc = bf2[tid];
+      #pragma unroll 10
+      for (int kk = 0; kk < N_H1; ++kk) acc += d3[kk] * wr[kk];
+      logits[tid] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float m = logits[0];
+      #pragma unroll
+      for (int i = 1; i < N_CLS; ++i) m = fmaxf(m, logits[i]);
+      float ssum = 0.f;
+      #pragma unroll
+      for (int i = 0; i < N_CLS; ++i) ssum += __expf(logits[i] - m);
+      const float lse = m + __logf(ssum);
+      float lp_t = 0.f;
+      const int64_t t = tgt[b];
+      #pragma unroll
+      for (int i = 0; i < N_CLS; ++i) {
+        const float lp = logits[i] - lse;
+        logp_ws[(int64_t)b * N_CLS + i] = lp;
+        if (i == (int)t) lp_t = lp;
+      }
+      lsum += -lp_t / B;
+    }
+    __syncthreads();
+    STAGE_STAMP(15);
+  }
+  if (tid == 0) {
+    if (loss_part) loss_part[blockIdx.x] = lsum;
+    else atomicAdd(loss, lsum);
   }
 }
 
@@ -1983,17 +2404,33 @@ static unsigned int* gw_cnt_buf(hipStream_t s) {
   return zeroed_once(bufs, GW_TILES, s);
 }
 
+// which forward kernel: the re-blocked 512-thread one up to B=256, the
+// 256-thread net_fwd_sample kernels (which the fwdbwd and single-launch
+// kernels share) above.  kernel_micro, forward alone: 10.8 vs 16.1 us at
+// B=64, 11.2-12.0 vs 16.5 at 128, 11.6 vs 17.5 at 192, 11.8 vs 17.6 at
+// 256, but 156.8 vs 120.8 at 4096: at 256 VGPRs and 60 KB of LDS a CU
+// holds one tiled workgroup, and three of the old ones.  Nothing was
+// measured between 256 and 4096, so those batches keep what they had.
+// DTP_FWD_TILED=0/1 overrides; read on every call, like DTP_BWD_TILED.
+static bool fwd_tiled(int B) {
+  if (const char* e = std::getenv("DTP_FWD_TILED")) return std::atoi(e) != 0;
+  return B <= 256;
+}
+
 // fwd sibling split: 2 workgroups per sample when one per sample
-// cannot fill the 256 CUs.  DTP_FWD_SPLIT=1 forces off, =2 forces on.
+// cannot fill the 256 CUs.  DTP_FWD_SPLIT=1 forces off, =2 forces on;
+// read on every call (the microbenchmark changes it between timings).
 static int fwd_split(int B) {
-  static const int env_v = env_int("DTP_FWD_SPLIT");
+  const int env_v = env_int("DTP_FWD_SPLIT");
   if (B * 2 > 4096) return 1;  // loss_part/flags hold 4096 entries
   if (env_v == 1) return 1;
   if (env_v == 2) return 2;
   // 3-rep A/B (profiles/sweeps/fsplit_reps.log): +1.5% at B=64, +0.6% at
   // B=128, -2.5% at B=192 (the pair grid exceeds the CU count there
   // and the exchange round trip is pure overhead) — so the split is
-  // a small-batch lever only.
+  // a small-batch lever only.  Re-measured with the tiled kernel: alone it
+  // is 0.5-0.9 us faster unsplit, in the step the split still wins (B=64
+  // 32.91 vs 33.63 us, B=128 39.10 vs 39.91; profiles/fwd_tiled_numbers.md).
   return B <= 128 ? 2 : 1;
 }
 
@@ -2033,19 +2470,25 @@ static unsigned long long* seed_bump(bool training, uintptr_t seed_dev) {
 // finalized by the kernel that ends the step.  Legacy mode (the autograd
 // path, net_fused_loss): a prologue dispatch zeroes the loss scalar and
 // the forward accumulates into it atomically.
-void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
-                   uintptr_t tgt, const std::vector<uintptr_t>& ws_v,
-                   bool use_loss_part, uintptr_t seed_dev, int B,
-                   bool training, uintptr_t stream) {
-  const NetWs w = net_ws(ws_v);
-  const GwPtrs prm = gw_ptrs(prm_v, "net_fused_fwd params");
-  float* loss_part = use_loss_part ? w.loss_part : nullptr;
-  if (!use_loss_part)
-    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0,
-                       S(stream), (unsigned long long*)nullptr, w.loss);
-  // the two forward kernels share their leading parameters
-  auto launch = [&](auto kern, int grid, auto... extra) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, S(stream),
+// how many polls sibling 0 of the tiled split forward waits for its
+// sibling's token before it computes that half itself
+constexpr int FWD_POLL_BOUND = 60000;
+
+// The one place that picks the forward's kernel, block size and grid:
+// tiled or net_fwd_sample kernels, split = 2 sibling workgroups per
+// sample (grid 2B, blockIdx = 2b + half) or one (grid_for(B, 1)).  The
+// four kernels share their leading parameters; poll_bound reaches the
+// tiled split kernel only (the old one polls 60000 times).
+static void launch_fwd(uintptr_t x, const GwPtrs& prm, uintptr_t tgt,
+                       const NetWs& w, float* loss_part, uintptr_t seed_dev,
+                       int B, bool training, bool tiled, int split,
+                       int poll_bound, hipStream_t s) {
+  if (tiled && (x & 15))
+    throw std::invalid_argument(
+        "net_fused_fwd: x must be 16-byte aligned (DTP_FWD_TILED=0 has "
+        "no such requirement)");
+  auto launch = [&](auto kern, int grid, int block, auto... extra) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, s,
                        (const float*)x, prm.p[G_W1], prm.p[G_B1],
                        prm.p[G_W2], prm.p[G_B2], prm.p[G_WF1], prm.p[G_BF1],
                        prm.p[G_WF2], prm.p[G_BF2], (const int64_t*)tgt, w.p1,
@@ -2054,11 +2497,51 @@ void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
                        (const unsigned long long*)seed_dev, B,
                        training ? 1 : 0, extra...);
   };
-  if (fwd_split(B) == 2)
-    launch(net_fused_fwd_split_kernel, 2 * B, fwd_flags_buf(S(stream)),
+  if (split == 2 && tiled)
+    launch(net_fused_fwd_tiled_kernel<true>, 2 * B, FT_NT, fwd_flags_buf(s),
+           fwd_token(), poll_bound);
+  else if (split == 2)
+    launch(net_fused_fwd_split_kernel, 2 * B, 256, fwd_flags_buf(s),
            fwd_token());
+  else if (tiled)
+    launch(net_fused_fwd_tiled_kernel<false>, grid_for(B, 1), FT_NT,
+           (unsigned int*)nullptr, 0u, 0);
   else
-    launch(net_fused_fwd_kernel, grid_for(B, 1));
+    launch(net_fused_fwd_kernel, grid_for(B, 1), 256);
+}
+
+void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
+                   uintptr_t tgt, const std::vector<uintptr_t>& ws_v,
+                   bool use_loss_part, uintptr_t seed_dev, int B,
+                   bool training, uintptr_t stream) {
+  const NetWs w = net_ws(ws_v);
+  const GwPtrs prm = gw_ptrs(prm_v, "net_fused_fwd params");
+  if (!use_loss_part)
+    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0,
+                       S(stream), (unsigned long long*)nullptr, w.loss);
+  launch_fwd(x, prm, tgt, w, use_loss_part ? w.loss_part : nullptr,
+             seed_dev, B, training, fwd_tiled(B), fwd_split(B),
+             FWD_POLL_BOUND, S(stream));
+}
+
+// raw forward launch in loss_part mode with the kernel, the sibling split
+// and the poll bound given (microbenchmarks; tests force the hand-off's
+// fallback with poll_bound 0).  The loss partials are those of a
+// split-`split` grid, whatever fwd_grid(B) says.
+void net_fwd_raw(uintptr_t x, const std::vector<uintptr_t>& prm_v,
+                 uintptr_t tgt, const std::vector<uintptr_t>& ws_v,
+                 uintptr_t seed_dev, int B, bool training, bool tiled,
+                 int split, int poll_bound, uintptr_t stream) {
+  if (B < 1) throw std::invalid_argument("net_fwd_raw: B must be >= 1");
+  if (split != 1 && split != 2)
+    throw std::invalid_argument("net_fwd_raw: split must be 1 or 2");
+  if (split == 2 && B * 2 > 4096)
+    throw std::invalid_argument("net_fwd_raw: split 2 needs B <= 2048");
+  if (poll_bound < 0)
+    throw std::invalid_argument("net_fwd_raw: poll_bound must be >= 0");
+  const NetWs w = net_ws(ws_v);
+  launch_fwd(x, gw_ptrs(prm_v, "net_fwd_raw params"), tgt, w, w.loss_part,
+             seed_dev, B, training, tiled, split, poll_bound, S(stream));
 }
 
 // sibling workgroups per sample of the data backward: enough to fill
@@ -2367,6 +2850,7 @@ void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
 
 void register_net_fused(pybind11::module_& m) {
   m.def("net_fused_fwd", &net_fused_fwd);
+  m.def("net_fwd_raw", &net_fwd_raw);
   m.def("net_fused_bwd", &net_fused_bwd);
   m.def("net_bwd_data_raw", &net_bwd_data_raw);
 #ifdef DTP_STAGE_STAMPS

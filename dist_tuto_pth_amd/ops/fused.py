@@ -2,8 +2,12 @@
 
 Four dispatches per training step instead of ~30 per-op launches:
 one kernel for the entire forward (conv1..log_softmax+NLL,
-train_dist.py:64-71 + :120, conv+pool register-fused, per-block loss
-partials), one for the data backward (sibling-workgroup split,
+train_dist.py:64-71 + :120; 512 threads, both convs as 2x8 output blocks
+fed by 16-byte LDS reads with the pool fused in registers, conv2's input
+channels split over lanes and summed through LDS in a fixed order, two
+sibling workgroups per sample at small batches, per-block loss partials;
+DTP_FWD_TILED=0 selects the earlier 256-thread kernels), one for the
+data backward (sibling-workgroup split,
 2x4-tile register-blocked transposed conv with the conv2 channels split
 over lanes), one segmented partial
 weight-gradient kernel ([conv2 x8 | conv1 x8 | fc1 | fc2] tiles x batch
