@@ -1,7 +1,7 @@
 // net_fused.hip — the fused whole-Net training step (gfx950/MI355X):
 // everything that hard-codes Net's architecture.  Device code first
-// (forward, data backward, weight-gradient partial / combine / fold,
-// the single-launch cooperative step), then the host layer: one
+// (forward, data backward, weight-gradient partial / combine, the
+// single-launch cooperative step), then the host layer: one
 // workspace layout, one chunk plan, one launcher per kernel group.
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_net_fused().
@@ -23,8 +23,7 @@ namespace py = pybind11;
 // Plain aggregates of pointers and ints.  Who takes them, in one place:
 //  - the host layer holds NetWs / GwPtrs and passes them, or their typed
 //    members, to every launch;
-//  - net_fused_fwdbwd_kernel and the two net_gw_partial_fold_kernel take
-//    them by value;
+//  - net_fused_fwdbwd_kernel takes them by value;
 //  - every other kernel and every device helper keeps a __restrict__
 //    pointer list.  The helpers because the stashes mix floats with bytes
 //    (idx1, m2, idx2, m3): a byte access may alias anything unless its
@@ -137,28 +136,22 @@ __device__ unsigned long long g_stage_stamps[STAGE_NBLK * STAGE_NSTAMP];
 #define STAGE_STAMP(i) do {} while (0)
 #endif
 
-// partial-row access, parameterized on coherence: the in-launch fold
-// variant stores partials sc1 (device-coherent, straight to the
-// coherence point) and reads them back sc1 — ZERO fences, so the
-// concurrently-running tile blocks keep their L1/L2 activation
-// locality.  The first fold attempt used the plain-store + agent
-// release/acquire recipe and measured 23-28% SLOWER end to end: one
-// `buffer_wbl2` L2 writeback per block x 1744 blocks evicted the very
-// activations the partial blocks re-read (ledger).  Partial traffic is
-// ~1.8 MB/step, so the slower sc1 store path is immaterial.
-template <bool SC1>
-__device__ __forceinline__ void gw_st(float* p, float v) {
-  if (SC1)
+// p2 access of the split forward's sibling hand-off.  ON: a relaxed
+// agent-scope (sc1) store or load, which goes to the device's coherence
+// point, so sibling 1's p2 half is visible to sibling 0 on another CU
+// once the stores have retired and the flag is written after them: no
+// fence, hence no cache writeback or invalidate under the workgroups
+// that run beside them.  The store is shared with the unsplit forward,
+// where it is a plain store (ON false); only sibling 0 loads.
+template <bool ON>
+__device__ __forceinline__ void sc1_st(float* p, float v) {
+  if (ON)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else
     *p = v;
 }
-template <bool SC1>
-__device__ __forceinline__ float gw_ld(const float* p) {
-  if (SC1)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-  return *p;
+__device__ __forceinline__ float sc1_ld(const float* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // One sample's full forward (conv1..log_softmax+NLL) by one 256-thread
@@ -293,7 +286,7 @@ __device__ __forceinline__ float net_fwd_sample(
       if (q11 > m) { m = q11; am = 3; }
       const float o = m > 0.f ? m : 0.f;
       p2[i] = o;
-      gw_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
+      sc1_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
       idx2_ws[(int64_t)b * N_P2 + i] = (uint8_t)(m > 0.f ? am : (am | 4));
     }
     if ((!SPLIT || half == 0) && training && tid < N_C2K) {
@@ -340,7 +333,7 @@ __device__ __forceinline__ float net_fwd_sample(
       __syncthreads();
       if (s_got) {
         for (int i = N_P2 / 2 + tid; i < N_P2; i += 256)
-          p2[i] = gw_ld<true>(p2_ws + (int64_t)b * N_P2 + i);
+          p2[i] = sc1_ld(p2_ws + (int64_t)b * N_P2 + i);
       } else {  // sibling never ran: do its channels from our own p1
         for (int i = N_P2 / 2 + tid; i < N_P2; i += 256) {
           const int k = i / 16, ph = (i / 4) % 4, pw = i % 4;
@@ -778,7 +771,7 @@ net_fused_fwd_tiled_kernel(
       const uint8_t ib = ft_pool(v[0], v[1], v[2], v[3], o);
       const int i = k0 * 16 + tid;
       p2[i] = o;
-      gw_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
+      sc1_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
       idx2_ws[(int64_t)b * N_P2 + i] = ib;
     }
     if ((!SPLIT || half == 0) && training && tid < N_C2K) {
@@ -819,7 +812,7 @@ net_fused_fwd_tiled_kernel(
       if (s_got) {
         if (tid < N_P2 / 2)
           p2[N_P2 / 2 + tid] =
-              gw_ld<true>(p2_ws + (int64_t)b * N_P2 + N_P2 / 2 + tid);
+              sc1_ld(p2_ws + (int64_t)b * N_P2 + N_P2 / 2 + tid);
       } else if (tid < N_P2 / 2) {
         // the sibling is not resident yet: its channels from our own p1
         // and w2 in global memory, one pooled cell per thread (cold, so
@@ -1485,7 +1478,6 @@ typedef float gw_f32x4 __attribute__((ext_vector_type(4)));
 // Every accumulator index is compile-time (a runtime index spilled to
 // scratch and tripled this kernel once — r2 ledger).
 static_assert(T_CONV2 * 32 >= 251, "conv2 gw column tiles cover 250 + bias");
-template <bool SC1 = false>
 __device__ __forceinline__ void net_gw_conv2_mfma(
     int nt, int tid, int b0, int b1, float* __restrict__ my,
     const float* __restrict__ p1_ws, const float* __restrict__ ga2_ws) {
@@ -1569,9 +1561,9 @@ __device__ __forceinline__ void net_gw_conv2_mfma(
     const int k = i >> 5, nn = nt * 32 + (i & 31);
     const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
     if (nn < 250)
-      gw_st<SC1>(my + OFF_W2 + k * 250 + nn, v);
+      *(my + OFF_W2 + k * 250 + nn) = v;
     else if (nn == 250)
-      gw_st<SC1>(my + OFF_B2 + k, v);
+      *(my + OFF_B2 + k) = v;
   }
 }
 
@@ -1588,7 +1580,6 @@ __device__ __forceinline__ void net_gw_conv2_mfma(
 // Lane map (16x16x4): A[row l&15][k l>>4], B[k l>>4][col l&15];
 // D[row 4*(l>>4) + reg][col l&15].  Two independent accumulator tiles
 // per wave cover the 40-clk dependent latency (32-clk issue).
-template <bool SC1 = false>
 __device__ __forceinline__ void net_gw_conv1_mfma(
     int sub, int tid, int b0, int b1, float* __restrict__ my,
     const float* __restrict__ x, const float* __restrict__ ga1_ws) {
@@ -1645,15 +1636,16 @@ __device__ __forceinline__ void net_gw_conv1_mfma(
   float* dst = (sub == 0) ? (my + OFF_W1)
                           : (my + GW_TOTAL + (sub - 1) * 260);
   for (int i = tid; i < 260; i += 256)
-    gw_st<SC1>(dst + i,
-               (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+    *(dst + i) = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
 
 // One (tile, batch-chunk) partial weight-gradient reduction.  Tiles
 // walk [conv2 x8 | conv1 x8 | fc1 | fc2]; partials land in my[GW_ROW]
 // laid out like the flat grad buffer.  Shared by net_gw_partial_kernel
-// and the single-launch net_step_kernel.
-template <bool SC1 = false>
+// and the single-launch net_step_kernel.  Partial rows are addressed
+// pointer first, `*(my + OFF + i)`, here and in net_gw_combine_elem:
+// `my[OFF + i]` sums the index in int before it is widened and changes
+// the address code of both kernels.
 __device__ __forceinline__ void net_gw_tile(
     int tile, int tid, int b0, int b1,
     float* __restrict__ my,
@@ -1668,7 +1660,7 @@ __device__ __forceinline__ void net_gw_tile(
   if (tile < T_CONV2) {  // conv2: gw [20][10][5][5] + gb [20]
     // one code path for every chunk size: a block is one 32-column
     // slice of the implicit GEMM over ALL 20 output channels
-    net_gw_conv2_mfma<SC1>(tile, tid, b0, b1, my, p1_ws, ga2_ws);
+    net_gw_conv2_mfma(tile, tid, b0, b1, my, p1_ws, ga2_ws);
     return;
   }
   tile -= T_CONV2;
@@ -1676,7 +1668,7 @@ __device__ __forceinline__ void net_gw_tile(
     // K (the 24 output rows x batch chunk) is split over T_CONV1
     // sub-blocks; sub 0 writes the canonical region, subs 1.. the
     // extension rows, which the combine folds.
-    net_gw_conv1_mfma<SC1>(tile, tid, b0, b1, my, x, ga1_ws);
+    net_gw_conv1_mfma(tile, tid, b0, b1, my, x, ga1_ws);
     return;
   }
   tile -= T_CONV1;
@@ -1698,12 +1690,12 @@ __device__ __forceinline__ void net_gw_tile(
           ae += gh1_ws[(int64_t)b * N_H1 + n] *
                 p2_ws[(int64_t)b * N_P2 + k];
         acc = ae + ao;
-        gw_st<SC1>(my + OFF_WF1 + i, acc);
+        *(my + OFF_WF1 + i) = acc;
       } else {
         const int n = i - 16000;
         for (int b = b0; b < b1; ++b)
           acc += gh1_ws[(int64_t)b * N_H1 + n];
-        gw_st<SC1>(my + OFF_BF1 + n, acc);
+        *(my + OFF_BF1 + n) = acc;
       }
     }
     return;
@@ -1718,12 +1710,12 @@ __device__ __forceinline__ void net_gw_tile(
         for (int b = b0; b < b1; ++b)
           acc += glog_ws[(int64_t)b * N_CLS + n] *
                  d3_ws[(int64_t)b * N_H1 + k];
-        gw_st<SC1>(my + OFF_WF2 + i, acc);
+        *(my + OFF_WF2 + i) = acc;
       } else {
         const int n = i - 500;
         for (int b = b0; b < b1; ++b)
           acc += glog_ws[(int64_t)b * N_CLS + n];
-        gw_st<SC1>(my + OFF_BF2 + n, acc);
+        *(my + OFF_BF2 + n) = acc;
       }
     }
   }
@@ -1759,10 +1751,9 @@ net_gw_partial_kernel(// pointer by pointer: with NetWs by value this kernel
               x, p1_ws, p2_ws, d3_ws, ga1_ws, ga2_ws, gh1_ws, glog_ws);
 }
 
-// combine: grads[i] = sum over chunks of part[c][i], written through
-// the 8 per-parameter pointers (which may alias one flat buffer).
-// sum flat-grad element i over the nch chunk rows (+ conv1 extension)
-template <bool SC1 = false>
+// The combine of net_step_kernel's phase 4, its only caller (the combine
+// kernels below have their own, wider one): sum flat-grad element i
+// over the chunk rows of part (+ the conv1 extension).
 __device__ __forceinline__ float net_gw_combine_elem(
     int i, int nch, int nch1, int nch2,
     const float* __restrict__ part) {
@@ -1779,27 +1770,29 @@ __device__ __forceinline__ float net_gw_combine_elem(
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   int c = 0;
   for (; c + 3 < n; c += 4) {
-    a0 += gw_ld<SC1>(part + (int64_t)c * GW_ROW + i);
-    a1 += gw_ld<SC1>(part + (int64_t)(c + 1) * GW_ROW + i);
-    a2 += gw_ld<SC1>(part + (int64_t)(c + 2) * GW_ROW + i);
-    a3 += gw_ld<SC1>(part + (int64_t)(c + 3) * GW_ROW + i);
+    a0 += *(part + (int64_t)c * GW_ROW + i);
+    a1 += *(part + (int64_t)(c + 1) * GW_ROW + i);
+    a2 += *(part + (int64_t)(c + 2) * GW_ROW + i);
+    a3 += *(part + (int64_t)(c + 3) * GW_ROW + i);
   }
-  for (; c < n; ++c) a0 += gw_ld<SC1>(part + (int64_t)c * GW_ROW + i);
+  for (; c < n; ++c) a0 += *(part + (int64_t)c * GW_ROW + i);
   if (i < 260) {  // conv1 sub-block extension rows (see GW_ROW)
     // fully unrolled over the 7 rows — a runtime-bound loop here cost
     // the combine 50% (8.1 -> 12.2 us, r2 ledger)
     static_assert(T_CONV1 == 8, "extension fold is unrolled for 7 rows");
     for (int c2 = 0; c2 < nch1; ++c2) {
       const float* ext = part + (int64_t)c2 * GW_ROW + GW_TOTAL;
-      a0 += gw_ld<SC1>(ext + i) + gw_ld<SC1>(ext + 4 * 260 + i);
-      a1 += gw_ld<SC1>(ext + 260 + i) + gw_ld<SC1>(ext + 5 * 260 + i);
-      a2 += gw_ld<SC1>(ext + 2 * 260 + i) + gw_ld<SC1>(ext + 6 * 260 + i);
-      a3 += gw_ld<SC1>(ext + 3 * 260 + i);
+      a0 += *(ext + i) + *(ext + 4 * 260 + i);
+      a1 += *(ext + 260 + i) + *(ext + 5 * 260 + i);
+      a2 += *(ext + 2 * 260 + i) + *(ext + 6 * 260 + i);
+      a3 += *(ext + 3 * 260 + i);
     }
   }
   return (a0 + a1) + (a2 + a3);
 }
 
+// which of the 8 tensors holds flat-grad element i (off: the 9 region
+// bounds); net_step_kernel's phase 4 only
 __device__ __forceinline__ int net_gw_tensor_of(int i, const int* off) {
   int t = 0;
   while (i >= off[t + 1]) ++t;
@@ -2034,130 +2027,6 @@ net_gw_combine_sgd_kernel(const float* __restrict__ part, GwPtrs g,
                             loss_part, loss_out, nblk_fwd, seed_bump);
 }
 
-// ---------------------------------------------------------------------------
-// In-launch gw fold (r2): the combine dispatch is pure latency (~10 us at
-// B=128 — 86 tiny blocks, an L2-chain fold of 1.4 MB of partials), so this
-// variant of the partial kernel deletes it: the LAST-ARRIVING block of each
-// tile column folds the region its column wrote (and, DO_SGD, applies the
-// momentum update), using the split-K last-arriver recipe from the CDNA
-// guide (G16): every block drains vmcnt + __syncthreads, lane 0 issues an
-// agent-scope RELEASE fence, restates the vmcnt wait, THEN takes a relaxed
-// agent-scope ticket; the block that draws target-1 acquires (agent) and
-// reads every row with plain loads.  Fold regions are per COLUMN (what the
-// column's own blocks wrote), so counter==target implies the region's rows
-// are all visible:
-//   conv2 column t  -> columns 32t..32t+31 of (c,r,s | bias), all 20
-//                      output channels
-//   conv1 family    -> ONE counter over all T_CONV1*nch blocks (its
-//                      sub-blocks share the 260 outputs via extension rows,
-//                      so no single column's completion suffices)
-//   fc1/fc2 column j -> its 256-element flat slice
-// Each fold runs as soon as ITS column's blocks are done — overlapped with
-// the other families still computing — so the only exposed cost is the
-// straggler family's own (tiny) fold.
-__device__ __forceinline__ void net_gw_fold_one(
-    int i, int nch, const float* __restrict__ part,
-    const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
-    float mu, bool do_sgd) {
-  const int off[9] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WF1, OFF_BF1,
-                      OFF_WF2, OFF_BF2, GW_TOTAL};
-  const float acc = net_gw_combine_elem<true>(i, nch, nch, nch, part);
-  const int t = net_gw_tensor_of(i, off);
-  const int64_t j = i - off[t];
-  g.p[t][j] = acc;
-  if (do_sgd) {
-    float v = acc;
-    if (buf.p[t]) {
-      v = mu * buf.p[t][j] + acc;
-      buf.p[t][j] = v;
-    }
-    prm.p[t][j] -= lr * v;
-  }
-}
-
-__device__ __forceinline__ void net_gw_fold_range(
-    int i0, int i1, int nch, const float* __restrict__ part,
-    const GwPtrs& g, const GwPtrs& prm, const GwPtrs& buf, float lr,
-    float mu, bool do_sgd) {
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256)
-    net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, do_sgd);
-}
-
-template <bool DO_SGD>
-__global__ void __launch_bounds__(256)
-net_gw_partial_fold_kernel(const float* __restrict__ x, NetWs ws, int B,
-                           int bchunk,
-                           GwPtrs g, GwPtrs prm, GwPtrs buf, float lr,
-                           float mu, const float* __restrict__ loss_part,
-                           float* __restrict__ loss_out, int nblk_fwd,
-                           unsigned long long* seed_bump,
-                           unsigned int* __restrict__ cnt) {
-  const int b0 = blockIdx.y * bchunk;
-  float* __restrict__ part = ws.part;
-  net_gw_tile<true>(blockIdx.x, threadIdx.x, b0, min(B, b0 + bchunk),
-                    part + (int64_t)blockIdx.y * GW_ROW, x, ws.p1, ws.p2,
-                    ws.d3, ws.ga1, ws.ga2, ws.gh1, ws.glog);
-  // ---- last-arriver ticket, FENCE-FREE: the tile wrote its partials
-  // with sc1 stores (already at the coherence point once vmcnt
-  // retires), so the ticket needs only the vmcnt drain before it and
-  // the reducer reads the rows back with sc1 loads.  No buffer_wbl2 /
-  // buffer_inv anywhere — the concurrent tile blocks keep their
-  // L1/L2-resident activations (the fenced variant cost 23-28%).
-  const int nch = (int)gridDim.y;
-  const int xcol = (int)blockIdx.x;
-  const bool conv1_fam = (xcol >= T_CONV2 && xcol < T_CONV2 + T_CONV1);
-  const int ci = conv1_fam ? T_CONV2 : xcol;
-  const unsigned target =
-      conv1_fam ? (unsigned)(T_CONV1 * nch) : (unsigned)nch;
-  __shared__ unsigned s_tk;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_tk = __hip_atomic_fetch_add(&cnt[ci], 1u, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (s_tk != target - 1) return;  // not the last arriver of this region
-  if (threadIdx.x == 0)
-    __hip_atomic_store(&cnt[ci], 0u, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);  // re-arm for next step
-  __syncthreads();
-  if (xcol < T_CONV2) {  // conv2: this column's 32-wide slice, all k
-    for (int e = (int)threadIdx.x; e < N_C2K * 32; e += 256) {
-      const int k = e >> 5, nn = xcol * 32 + (e & 31);
-      if (nn > 250) continue;
-      const int i = nn < 250 ? OFF_W2 + k * 250 + nn : OFF_B2 + k;
-      net_gw_fold_one(i, nch, part, g, prm, buf, lr, mu, DO_SGD);
-    }
-    return;
-  }
-  if (conv1_fam) {  // conv1: canonical 260 + extension rows
-    net_gw_fold_range(0, 260, nch, part, g, prm, buf, lr, mu,
-                      DO_SGD);
-    return;
-  }
-  if (xcol < T_CONV2 + T_CONV1 + T_FC1) {  // fc1 column slice
-    const int i0 = OFF_WF1 + (xcol - (T_CONV2 + T_CONV1)) * 256;
-    net_gw_fold_range(i0, min(OFF_WF1 + 16050, i0 + 256), nch, part, g, prm, buf, lr, mu, DO_SGD);
-    return;
-  }
-  // fc2 column slice; the last column also finalizes the loss partials
-  // and advances the dropout seed (wave 0 only — no extra LDS).
-  const int i0 = OFF_WF2 + (xcol - (T_CONV2 + T_CONV1 + T_FC1)) * 256;
-  net_gw_fold_range(i0, min(OFF_WF2 + 510, i0 + 256), nch, part,
-                    g, prm, buf, lr, mu, DO_SGD);
-  if (xcol == GW_TILES - 1 && threadIdx.x < 64) {
-    if (loss_part) {
-      float v = 0.f;
-      for (int i = threadIdx.x; i < nblk_fwd; i += 64) v += loss_part[i];
-      #pragma unroll
-      for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-      if (threadIdx.x == 0 && loss_out) *loss_out = v;
-    }
-    if (threadIdx.x == 0 && seed_bump)
-      *seed_bump += SEED_INC;
-  }
-}
-
 // ===========================================================================
 // Single-launch training step (cooperative kernel).
 //
@@ -2326,37 +2195,11 @@ static GwPtrs buf_ptrs(const std::vector<uintptr_t>& v) {
   return g;
 }
 
-// a per-device u32 buffer of n entries, allocated and zeroed once
-// (bufs: the caller's function-local static, one slot per device)
-static unsigned int* zeroed_once(unsigned int* (&bufs)[64], size_t n,
-                                 hipStream_t s) {
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
-  if (!bufs[dev]) {
-    HIP_CHECK(hipMalloc(&bufs[dev], n * sizeof(unsigned int)));
-    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, n * sizeof(unsigned int), s));
-  }
-  return bufs[dev];
-}
-
 // integer environment variable (0 when unset); callers that may read
 // it once per process keep the result in a function-local static
 static int env_int(const char* name) {
   const char* e = std::getenv(name);
   return e ? std::atoi(e) : 0;
-}
-
-// in-launch gw fold (last-arriver epilogue in the partial kernel, no
-// combine dispatch).  DTP_GW_FOLD=1 opts in; the default stays the
-// two-kernel path — MEASURED NEGATIVE on both step shapes (ledger):
-// the combine's dispatch latency is hidden by the stream pipeline
-// (kernels enqueue back-to-back), so only its ~5 us execution is
-// exposed, while the epilogue's per-block sc1-drain tail costs ~4-5 us
-// across the critical path at B=128 (-5%); parity at B>=512.
-static bool gw_fold_on() {
-  static const bool on = env_int("DTP_GW_FOLD") != 0;
-  return on;
 }
 
 // Batch chunking of the weight-gradient partial kernel, one chunk count
@@ -2373,7 +2216,6 @@ static bool gw_fold_on() {
 //   nch2 (conv2), the family with the most arithmetic: 24 up to B=192
 //        (B=128 55.2 us vs 56.1 at 32, 56.9 at 16), above that the most
 //        rows the workspace holds (B=512 105.8 us at 32 vs 106.8 at 24).
-// The fold path keeps uniform chunks (its per-column tickets assume it).
 // gy is the partial kernel's gridDim.y.
 struct GwPlan { int nch, nch1, nch2, bchunk, bchunk1, bchunk2, gy; };
 
@@ -2384,24 +2226,13 @@ static GwPlan gw_plan(int B) {
   auto clamp = [B](int n) { return std::min(n, std::min(GW_MAX_CH, B)); };
   GwPlan p;
   p.nch = clamp(env_nch > 0 ? env_nch : (B <= 192 ? 16 : 24));
-  if (gw_fold_on()) {
-    p.nch1 = p.nch2 = p.nch;
-  } else {
-    p.nch1 = clamp(env_nch1 > 0 ? env_nch1 : p.nch);
-    p.nch2 = clamp(env_nch2 > 0 ? env_nch2 : (B <= 192 ? 24 : 32));
-  }
+  p.nch1 = clamp(env_nch1 > 0 ? env_nch1 : p.nch);
+  p.nch2 = clamp(env_nch2 > 0 ? env_nch2 : (B <= 192 ? 24 : 32));
   p.bchunk = (B + p.nch - 1) / p.nch;
   p.bchunk1 = (B + p.nch1 - 1) / p.nch1;
   p.bchunk2 = (B + p.nch2 - 1) / p.nch2;
   p.gy = std::max(p.nch, std::max(p.nch1, p.nch2));
   return p;
-}
-
-// per-device ticket counters for the fold epilogue (GW_TILES u32,
-// zeroed once; each reducer re-arms its own counter every step)
-static unsigned int* gw_cnt_buf(hipStream_t s) {
-  static unsigned int* bufs[64] = {};
-  return zeroed_once(bufs, GW_TILES, s);
 }
 
 // which forward kernel: the re-blocked 512-thread one up to B=256, the
@@ -2451,17 +2282,26 @@ static unsigned int fwd_token() {
   return t;
 }
 
-// per-device per-sample handshake flags for the split fwd (zeroed
-// once; published tokens are step-unique, no re-arm needed)
+// per-device per-sample handshake flags for the split fwd (4096 u32,
+// allocated and zeroed once; published tokens are step-unique, no
+// re-arm needed)
 static unsigned int* fwd_flags_buf(hipStream_t s) {
   static unsigned int* bufs[64] = {};
-  return zeroed_once(bufs, 4096, s);
+  constexpr size_t bytes = 4096 * sizeof(unsigned int);
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) throw std::runtime_error("device index > 64");
+  if (!bufs[dev]) {
+    HIP_CHECK(hipMalloc(&bufs[dev], bytes));
+    HIP_CHECK(hipMemsetAsync(bufs[dev], 0, bytes, s));
+  }
+  return bufs[dev];
 }
 
 // Seed convention of every fused path: a training step CONSUMES the
-// device seed and the kernel that ends the step (combine / fold
-// epilogue) ADVANCES it, so the autograd path and the step paths can
-// interleave without mask reuse.  Null = leave the seed alone.
+// device seed and the kernel that ends the step (the combine) ADVANCES
+// it, so the autograd path and the step paths can interleave without
+// mask reuse.  Null = leave the seed alone.
 static unsigned long long* seed_bump(bool training, uintptr_t seed_dev) {
   return training ? (unsigned long long*)seed_dev : nullptr;
 }
@@ -2585,23 +2425,15 @@ static void launch_bwd_data(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
 
 // Weight gradients, the end of every multi-dispatch step: one segmented
 // partial kernel over the gw_plan chunks + one combine (no memsets, no
-// atomics; any batch size), or the opt-in fold kernel.  With `sgd` the
-// combine also applies the SGD+momentum update.  The kernel that ends
-// the step folds the nblk_fwd per-block loss partials into loss_out
-// (both null in legacy mode) and advances *seed (null = no bump).
+// atomics; any batch size).  With `sgd` the combine also applies the
+// SGD+momentum update.  It ends the step: it sums the nblk_fwd
+// per-block loss partials into loss_out (both null in legacy mode) and
+// advances *seed (null = no bump).
 static void launch_gw(const float* x, const NetWs& w, int B, GwPtrs gp,
                       GwPtrs pp, GwPtrs bp, float lr, float mu, bool sgd,
                       const float* loss_part, float* loss_out, int nblk_fwd,
                       unsigned long long* seed, hipStream_t s) {
   const GwPlan pl = gw_plan(B);
-  if (gw_fold_on()) {
-    auto* kern = !sgd ? net_gw_partial_fold_kernel<false>
-                      : net_gw_partial_fold_kernel<true>;
-    hipLaunchKernelGGL(kern, dim3(GW_TILES, pl.nch), dim3(256), 0, s, x, w,
-                       B, pl.bchunk, gp, pp, bp, lr, mu, loss_part,
-                       loss_out, nblk_fwd, seed, gw_cnt_buf(s));
-    return;
-  }
   hipLaunchKernelGGL(net_gw_partial_kernel, dim3(GW_TILES, pl.gy),
                      dim3(256), 0, s, x, w.p1, w.p2, w.d3, w.ga1, w.ga2,
                      w.gh1, w.glog, w.part, B, pl.bchunk, pl.bchunk1,

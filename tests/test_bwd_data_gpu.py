@@ -208,8 +208,9 @@ torch.save(out, sys.argv[1])
 def test_forward_sibling_split_on_and_off_agree(tmp_path):
     """The forward's sibling hand-off against the one-workgroup forward
     (what the hand-off's fallback computes): DTP_FWD_SPLIT=1 and =2 in two
-    fresh processes (the variable is read once per process), every batch,
-    eval and train; each process starts from the same dropout seed."""
+    fresh processes, every batch, eval and train.  The variable is read on
+    every call; the processes are fresh so that each starts from the same
+    dropout seed."""
     got = {}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for v in ("1", "2"):

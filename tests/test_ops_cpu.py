@@ -164,7 +164,7 @@ def test_gw_chunk_plan_and_exported_constants():
     import os
     import pytest
     from dist_tuto_pth_amd.utils.native import load_native
-    for v in ("DTP_GW_NCH", "DTP_GW_NCH1", "DTP_GW_NCH2", "DTP_GW_FOLD"):
+    for v in ("DTP_GW_NCH", "DTP_GW_NCH1", "DTP_GW_NCH2"):
         if v in os.environ:
             pytest.skip(f"{v} overrides the default chunk plan")
     k = load_native("_kernels")
