@@ -346,39 +346,6 @@ __global__ __launch_bounds__(BLK) void conv_bf16_bwd_w_kernel(
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-struct ConvDims {
-  int B, C, H, W, K, R, S, sh, sw, ph, pw;
-  int OH, OW;
-};
-
-// GEMM row/column/reduction counts are ints in the kernel and tile origins
-// go up to one tile past them; flattened element indices are int64.
-constexpr int64_t MAX_DIM = 2147483647LL - 2 * BM;
-
-static ConvDims conv_dims(int B, int C, int H, int W, int K, int R, int S_,
-                          int sh, int sw, int ph, int pw) {
-  if (B < 1 || C < 1 || H < 1 || W < 1 || K < 1 || R < 1 || S_ < 1)
-    throw std::invalid_argument("conv2d_bf16: every dimension must be >= 1");
-  if (sh < 1 || sw < 1 || ph < 0 || pw < 0)
-    throw std::invalid_argument(
-        "conv2d_bf16: stride must be >= 1 and padding >= 0");
-  const int64_t oh = ((int64_t)H + 2LL * ph - R) / sh + 1;
-  const int64_t ow = ((int64_t)W + 2LL * pw - S_) / sw + 1;
-  if ((int64_t)H + 2LL * ph < R || (int64_t)W + 2LL * pw < S_ || oh < 1 ||
-      ow < 1)
-    throw std::invalid_argument("conv2d_bf16: output would be empty");
-  const int64_t lim[] = {
-      (int64_t)B * oh * ow, (int64_t)B * H * W, (int64_t)C * R * S_,
-      (int64_t)K * R * S_,  (int64_t)H + 2LL * ph, (int64_t)W + 2LL * pw,
-      (int64_t)H * W,       oh * ow};
-  for (int64_t v : lim)
-    if (v > MAX_DIM)
-      throw std::invalid_argument(
-          "conv2d_bf16: a GEMM dimension does not fit the kernel's 32-bit "
-          "index");
-  return ConvDims{B, C, H, W, K, R, S_, sh, sw, ph, pw, (int)oh, (int)ow};
-}
-
 static ConvSrc src_x(uintptr_t x, const ConvDims& d) {  // forward, gw
   return ConvSrc{(const bf16_t*)x, d.C,  d.H,  d.W,  d.OH, d.OW,
                  d.R,              d.S,  d.sh, d.sw, d.ph, d.pw,

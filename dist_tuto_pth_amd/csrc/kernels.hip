@@ -796,13 +796,15 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 // K3-K6 (pool, ReLU, dropout and the bf16 cast, both dtypes) live in
 // pointwise.hip, the fused whole-Net step in net_fused.hip, K16 (bf16 MFMA
 // linear) in linear_bf16.hip, K17 (bf16 MFMA convolution) in
-// conv_bf16.hip, K18 (batch normalization with fused add and ReLU) in
-// batchnorm.hip, K19/K20 (general pooling) in pool.hip, K21 (cross-entropy
-// for wide rows) in cross_entropy.hip
+// conv_bf16.hip and, for channels-last tensors, conv_nhwc_bf16.hip, K18
+// (batch normalization with fused add and ReLU) in batchnorm.hip, K19/K20
+// (general pooling) in pool.hip, K21 (cross-entropy for wide rows) in
+// cross_entropy.hip
 void register_pointwise(pybind11::module_& m);
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
+void register_conv_nhwc_bf16(pybind11::module_& m);
 void register_batchnorm(pybind11::module_& m);
 void register_pool(pybind11::module_& m);
 void register_cross_entropy(pybind11::module_& m);
@@ -836,6 +838,7 @@ PYBIND11_MODULE(_kernels, m) {
   register_net_fused(m);
   register_linear_bf16(m);
   register_conv_bf16(m);
+  register_conv_nhwc_bf16(m);
   register_batchnorm(m);
   register_pool(m);
   register_cross_entropy(m);

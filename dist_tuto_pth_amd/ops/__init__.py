@@ -13,6 +13,8 @@ in ``csrc/pointwise.hip``, K16-K21 in the files named at their sections):
   K7/K8  linear (+fused ReLU epilogue)     -> linear
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
+         the same on channels-last storage  -> conv2d_bf16(memory_format=
+                                              torch.channels_last)
   K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d
   K19    maxpool2d (kernel, stride, padding) -> maxpool2d (fp32, bf16)
   K20    global average pool [B,C,H,W]->[B,C] -> global_avgpool2d
@@ -699,8 +701,129 @@ class _Conv2dBf16(torch.autograd.Function):
         return gx, gw, gb, None, None, None
 
 
+def _as_nhwc(t):
+    """``t`` [B,C,H,W] with dense channels-last storage (no copy where it
+    has that already)."""
+    return t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _to_bf16_nhwc(t):
+    """RNE cast to a bf16 tensor with dense channels-last storage.  The cast
+    kernel is elementwise, so it rounds the storage in whatever order it
+    lies."""
+    t = _as_nhwc(t)
+    if t.dtype == torch.bfloat16:
+        return t
+    if not t.is_cuda:
+        return t.to(torch.bfloat16)
+    out = torch.empty_like(t, dtype=torch.bfloat16)
+    _k().cast_f32_to_bf16(t.data_ptr(), out.data_ptr(), t.numel(),
+                          _stream())
+    return out
+
+
+def _empty_nhwc(B, C, H, W, like, dtype):
+    return torch.empty(B, H, W, C, device=like.device,
+                       dtype=dtype).permute(0, 3, 1, 2)
+
+
+class _Conv2dNhwcBf16(torch.autograd.Function):
+    """conv2d_bf16 on channels-last storage (csrc/conv_nhwc_bf16.hip): the
+    logical shapes are _Conv2dBf16's, activations lie [B][H][W][C]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, padding, out_dtype):
+        B, C, H, W = x.shape
+        K, _, R, S = w.shape
+        (sh, sw), (ph, pw) = stride, padding
+        OH = (H + 2 * ph - R) // sh + 1
+        OW = (W + 2 * pw - S) // sw + 1
+        ctx.x_dtype, ctx.w_dtype = x.dtype, w.dtype
+        if x.is_cuda:
+            k = _k()
+            xb, w = _to_bf16_nhwc(x), w.contiguous()
+            # [K][R][S][C], rounded to bf16 on the way
+            wp = torch.empty(K, R, S, C, device=x.device,
+                             dtype=torch.bfloat16)
+            k.conv2d_nhwc_bf16_pack_w(w.data_ptr(), wp.data_ptr(), K, C, R, S,
+                                      w.dtype == torch.float32, False,
+                                      _stream())
+            out = _empty_nhwc(B, K, OH, OW, x, out_dtype)
+            k.conv2d_nhwc_bf16_fwd(
+                xb.data_ptr(), wp.data_ptr(), _ptr(b), out.data_ptr(),
+                B, C, H, W, K, R, S, sh, sw, ph, pw,
+                out_dtype == torch.float32, _stream())
+        else:
+            # the default path's arithmetic, so the values are its bits
+            xb, w = _to_bf16(x), _to_bf16(w)
+            out = _as_nhwc(F.conv2d(xb.float(), w.float(), b, stride,
+                                    padding).to(out_dtype))
+        # on GPU the master weight: backward packs it again, for gx
+        ctx.save_for_backward(xb, w)
+        ctx.geom = (stride, padding, OH, OW)
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        xb, w = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        B, C, H, W = xb.shape
+        K, _, R, S = w.shape
+        stride, padding, OH, OW = ctx.geom
+        (sh, sw), (ph, pw) = stride, padding
+        gx = gw = gb = None
+        if xb.is_cuda:
+            k = _k()
+            gyb = _to_bf16_nhwc(gy)
+            dims = (B, C, H, W, K, R, S, sh, sw, ph, pw)
+            if need_x:
+                wp = torch.empty(C, R, S, K, device=xb.device,
+                                 dtype=torch.bfloat16)
+                k.conv2d_nhwc_bf16_pack_w(w.data_ptr(), wp.data_ptr(), K, C,
+                                          R, S, w.dtype == torch.float32,
+                                          True, _stream())
+                gx = _empty_nhwc(B, C, H, W, xb, ctx.x_dtype)  # fully written
+                k.conv2d_nhwc_bf16_bwd_x(
+                    gyb.data_ptr(), wp.data_ptr(), gx.data_ptr(), *dims,
+                    ctx.x_dtype == torch.float32, _stream())
+            if need_w or need_b:
+                n_gw = K * C * R * S
+                gw = torch.empty(K, C, R, S, device=xb.device,
+                                 dtype=torch.float32)
+                gb = torch.empty(K, device=xb.device, dtype=torch.float32) \
+                    if need_b else None
+                # gb is the row sum of the gw GEMM's gy tile, so a bias that
+                # alone needs a gradient still runs that GEMM and drops gw
+                # (as the NCHW path does); no layer here trains only a bias
+                splits = k.conv2d_nhwc_bf16_gw_splits(*dims)
+                part = torch.empty(splits * (n_gw + K), device=xb.device,
+                                   dtype=torch.float32) \
+                    if splits > 1 else None
+                k.conv2d_nhwc_bf16_bwd_w(
+                    gyb.data_ptr(), xb.data_ptr(), gw.data_ptr(), _ptr(gb),
+                    _ptr(part), splits, *dims, _stream())
+                if ctx.w_dtype == torch.bfloat16:
+                    gw = _to_bf16(gw)
+                if not need_w:
+                    gw = None
+            return gx, gw, gb, None, None, None
+        g = _to_bf16(gy).float()
+        if need_x:
+            gx = _as_nhwc(torch.nn.grad.conv2d_input(
+                xb.shape, w.float(), g, stride, padding).to(ctx.x_dtype))
+        if need_w:
+            gw = torch.nn.grad.conv2d_weight(
+                xb.float(), w.shape, g, stride, padding).to(ctx.w_dtype)
+        if need_b:
+            gb = g.sum(dim=(0, 2, 3))
+        return gx, gw, gb, None, None, None
+
+
 def conv2d_bf16(x, w, b=None, stride=1, padding=0,
-                out_dtype=torch.bfloat16):
+                out_dtype=torch.bfloat16,
+                memory_format=torch.contiguous_format):
     """2-D convolution (cross-correlation, NCHW) with bf16 operands and
     fp32 accumulation.
 
@@ -711,7 +834,19 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
     fused activation.  Backward gives ``gx`` in ``x``'s dtype (exact zeros
     where no output reads the input), ``gb`` in fp32 and ``gw`` in fp32
     for an fp32 (master) weight, or rounded once to bf16 for a bf16
-    weight; ``gw`` and ``gb`` are bitwise reproducible."""
+    weight; ``gw`` and ``gb`` are bitwise reproducible.
+
+    ``memory_format=torch.channels_last`` runs the same contract on
+    channels-last storage (K17's kernels in csrc/conv_nhwc_bf16.hip): ``x``
+    and, in backward, ``gy`` keep their logical [B,C,H,W] shape and are
+    brought to [B][H][W][C] storage, which costs nothing where they have it;
+    the result and ``gx`` come back with that storage, ``gw`` dense
+    [K,C,R,S].  The layout is never taken from ``x``'s strides: any other
+    value than these two raises ``ValueError``."""
+    if memory_format not in (torch.contiguous_format, torch.channels_last):
+        raise ValueError(f"conv2d_bf16: memory_format must be "
+                         f"torch.contiguous_format or torch.channels_last, "
+                         f"got {memory_format}")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"conv2d_bf16: out_dtype must be torch.bfloat16 or "
                         f"torch.float32, got {out_dtype}")
@@ -754,6 +889,8 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
                     ("out", B * K * OH * OW)):
         if v >= 2 ** 62:
             raise ValueError(f"conv2d_bf16: {what} has too many elements")
+    if memory_format == torch.channels_last:
+        return _Conv2dNhwcBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
     return _Conv2dBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
 
 
