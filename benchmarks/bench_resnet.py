@@ -50,6 +50,11 @@ def main():
                    help="build the model with compute_dtype=bfloat16: "
                         "convs, BN and the classifier on this package's "
                         "own HIP ops; autocast and channels_last are off")
+    p.add_argument("--memory-format", default="contiguous",
+                   choices=["contiguous", "channels_last"],
+                   help="with --compute-dtype bf16: channels_last builds "
+                        "the model with memory_format=torch.channels_last, "
+                        "its own HIP ops on [B][H][W][C] storage")
     p.add_argument("--own-step", action="store_true",
                    help="with --compute-dtype bf16: the loss is "
                         "ops.cross_entropy and the optimizer FusedSGD "
@@ -59,6 +64,9 @@ def main():
     own_bf16 = args.compute_dtype == "bf16"
     if args.own_step and not own_bf16:
         p.error("--own-step needs --compute-dtype bf16")
+    own_nhwc = args.memory_format == "channels_last"
+    if own_nhwc and not own_bf16:
+        p.error("--memory-format channels_last needs --compute-dtype bf16")
     if own_bf16:
         args.channels_last = False
         args.dtype = "fp32"      # no autocast: the model casts itself
@@ -80,8 +88,12 @@ def main():
     device = f"cuda:{dev_idx}"
 
     torch.manual_seed(1234)
-    model = (resnet50(compute_dtype=torch.bfloat16) if own_bf16
-             else resnet50()).to(device)
+    if own_nhwc:
+        model = resnet50(compute_dtype=torch.bfloat16,
+                         memory_format=torch.channels_last).to(device)
+    else:
+        model = (resnet50(compute_dtype=torch.bfloat16) if own_bf16
+                 else resnet50()).to(device)
     if args.channels_last:
         model = model.to(memory_format=torch.channels_last)
     if world > 1:
@@ -175,6 +187,7 @@ def main():
                        args.batch * world, "input": "3x224x224",
                        "parallelism": f"dp{world}",
                        "channels_last": args.channels_last,
+                       "memory_format": args.memory_format,
                        "miopen_find": not args.no_find,
                        "grad_sync": "average_gradients"
                        if args.no_overlap else

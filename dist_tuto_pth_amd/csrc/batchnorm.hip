@@ -38,17 +38,19 @@
 // tree, the 64 lanes by wave shuffles, the 4 waves through LDS.
 //
 // The access (load_vec / store_vec), the two sums (tree8, block_sum) and
-// the dispatch on dtype and width (by_dtype_width) are common.h's.
+// the dispatch on dtype and width (by_dtype_width, pick_v) are common.h's;
+// the two finalize kernels, channel_stats and the size guard are
+// bn_shared.h's, shared with the channels-last kernels of
+// batchnorm_nhwc.hip.
 //
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_batchnorm().
 
-#include "common.h"
+#include "bn_shared.h"
 
 #include <pybind11/pybind11.h>
 
 #include <algorithm>
-#include <initializer_list>
 
 namespace {
 
@@ -132,43 +134,6 @@ __global__ __launch_bounds__(BLK) void bn_stats_kernel(
   }
 }
 
-__global__ void bn_finalize_kernel(const float* __restrict__ ws, int C, int S,
-                                   float eps, float momentum,
-                                   float* __restrict__ save_mean,
-                                   float* __restrict__ save_invstd,
-                                   float* __restrict__ run_mean,
-                                   float* __restrict__ run_var) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float* p = ws + (int64_t)c * S * 3;
-  float n = p[0], mean = p[1], m2 = p[2];
-  for (int s = 1; s < S; ++s) {  // Chan's merge, in index order
-    const float nb = p[3 * s], mb = p[3 * s + 1], m2b = p[3 * s + 2];
-    const float nab = n + nb, delta = mb - mean;
-    mean += delta * (nb / nab);
-    m2 += m2b + delta * delta * (n * (nb / nab));
-    n = nab;
-  }
-  const float var = m2 / n;
-  save_mean[c] = mean;
-  save_invstd[c] = 1.f / sqrtf(var + eps);
-  if (run_mean) {
-    const float keep = 1.f - momentum;
-    run_mean[c] = keep * run_mean[c] + momentum * mean;
-    run_var[c] = keep * run_var[c] + momentum * (var * (n / (n - 1.f)));
-  }
-}
-
-// per-channel (mean, invstd): the saved statistics in training, the running
-// ones in eval (stat = running_var there)
-__device__ __forceinline__ void channel_stats(const float* mean,
-                                              const float* stat, float eps,
-                                              int eval, uint32_t c, float& mu,
-                                              float& inv) {
-  mu = mean[c];
-  inv = eval ? 1.f / sqrtf(stat[c] + eps) : stat[c];
-}
-
 // ---------------------------------------------------------------------------
 // forward apply (+ residual, + ReLU)
 // ---------------------------------------------------------------------------
@@ -248,21 +213,6 @@ __global__ __launch_bounds__(BLK) void bn_bwd_reduce_kernel(
   }
 }
 
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ ws, int C,
-                                       int S, float* __restrict__ dgamma,
-                                       float* __restrict__ dbeta) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float* p = ws + (int64_t)c * S * 2;
-  float db = p[0], dg = p[1];
-  for (int s = 1; s < S; ++s) {
-    db += p[2 * s];
-    dg += p[2 * s + 1];
-  }
-  dbeta[c] = db;
-  dgamma[c] = dg;
-}
-
 template <typename T, int V>
 __global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ gy,
@@ -310,17 +260,6 @@ __global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-constexpr int64_t MAX_ELEMS = (int64_t)1 << 31;  // 32-bit access indices
-
-void check_dims(int64_t B, int64_t C, int64_t HW) {
-  if (B < 1 || C < 1 || HW < 1)
-    throw std::invalid_argument("batchnorm2d: B, C and H*W must be >= 1");
-  if (B >= MAX_ELEMS || C >= MAX_ELEMS || HW >= MAX_ELEMS ||
-      B * C >= MAX_ELEMS || B * C * HW >= MAX_ELEMS)
-    throw std::invalid_argument(
-        "batchnorm2d: more than 2^31 - 1 elements are not supported");
-}
-
 // How many slices the planes of one channel are split into.  Enough blocks
 // to fill the chip when channels are few (aim: 8 per CU on 256 CUs), but a
 // slice keeps at least 2048 elements (8 per thread), so many channels of
@@ -333,16 +272,6 @@ int batchnorm2d_splits(int64_t B, int64_t C, int64_t HW) {
   if (s < 1) s = 1;
   const int64_t per = (B + s - 1) / s;  // planes per slice
   return (int)((B + per - 1) / per);    // no empty slice
-}
-
-// widest access (in elements) that is aligned for every plane and pointer
-int pick_v(int elem_bytes, int64_t HW, std::initializer_list<uintptr_t> ptrs) {
-  for (int v = 16 / elem_bytes; v > 1; v >>= 1) {
-    bool ok = HW % v == 0;
-    for (uintptr_t p : ptrs) ok = ok && p % (uintptr_t)(v * elem_bytes) == 0;
-    if (ok) return v;
-  }
-  return 1;
 }
 
 int planes_per_slice(int64_t B, int64_t C, int64_t HW, int S) {

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -63,6 +64,7 @@ __device__ __forceinline__ void from_f(float v, bf16_t& o) { o = f2bf(v); }
 // guarantees that p is aligned to the access: sizeof(T)*V bytes, 16 for the
 // 32-byte one, which is two 16-byte accesses.
 template <int BYTES> struct Raw;
+template <> struct Raw<1> { using type = uint8_t; };
 template <> struct Raw<2> { using type = uint16_t; };
 template <> struct Raw<4> { using type = uint32_t; };
 template <> struct Raw<8> { using type = uint2; };
@@ -141,6 +143,19 @@ void by_dtype(bool bf16, F&& f) {
 }
 template <class P>
 using elem_t = std::remove_pointer_t<P>;
+
+// widest access (in elements) that divides `run` — the length of the
+// contiguous axis: H*W for NCHW planes, C for channels-last rows — and is
+// aligned for every pointer
+inline int pick_v(int elem_bytes, int64_t run,
+                  std::initializer_list<uintptr_t> ptrs) {
+  for (int v = 16 / elem_bytes; v > 1; v >>= 1) {
+    bool ok = run % v == 0;
+    for (uintptr_t p : ptrs) ok = ok && p % (uintptr_t)(v * elem_bytes) == 0;
+    if (ok) return v;
+  }
+  return 1;
+}
 
 template <class F>
 void by_dtype_width(bool bf16, int v, F&& f) {

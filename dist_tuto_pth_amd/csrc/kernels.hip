@@ -806,7 +806,9 @@ void register_linear_bf16(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
 void register_conv_nhwc_bf16(pybind11::module_& m);
 void register_batchnorm(pybind11::module_& m);
+void register_batchnorm_nhwc(pybind11::module_& m);
 void register_pool(pybind11::module_& m);
+void register_pool_nhwc(pybind11::module_& m);
 void register_cross_entropy(pybind11::module_& m);
 
 PYBIND11_MODULE(_kernels, m) {
@@ -840,6 +842,8 @@ PYBIND11_MODULE(_kernels, m) {
   register_conv_bf16(m);
   register_conv_nhwc_bf16(m);
   register_batchnorm(m);
+  register_batchnorm_nhwc(m);
   register_pool(m);
+  register_pool_nhwc(m);
   register_cross_entropy(m);
 }

@@ -29,6 +29,13 @@ global average pool is ``ops.global_avgpool2d``, which already returns
 [B,C]: no op of this mode's forward or backward is borrowed from torch.
 ``num_batches_tracked`` is not touched: torch reads it only when
 ``momentum=None``, which ``ops.batchnorm2d`` does not support.
+
+``memory_format=torch.channels_last`` (only with
+``compute_dtype=torch.bfloat16``) passes that keyword to every conv, BN and
+pool of the bf16 forward.  The stem conv lays the input batch out
+[B][H][W][C]; from there to the [B,C] pooled vector every activation and
+every gradient has channels-last storage, so no op copies a layout.
+Parameters, buffers and ``state_dict`` are the same in both layouts.
 """
 
 from __future__ import annotations
@@ -49,25 +56,49 @@ def _check_compute_dtype(who, compute_dtype):
     return compute_dtype
 
 
-def _conv_bf16(conv, x):
+def _check_memory_format(who, memory_format, compute_dtype):
+    if memory_format not in (torch.contiguous_format, torch.channels_last):
+        raise ValueError(
+            f"{who}: memory_format must be torch.contiguous_format or "
+            f"torch.channels_last, got {memory_format}")
+    if memory_format == torch.channels_last and compute_dtype is None:
+        raise ValueError(
+            f"{who}: memory_format=torch.channels_last needs "
+            f"compute_dtype=torch.bfloat16")
+    return memory_format
+
+
+def _layout_kw(memory_format):
+    """What the bf16 forward adds to every conv, BN and pool call: nothing
+    in the default layout, whose calls stay exactly as they were."""
+    if memory_format == torch.channels_last:
+        return {"memory_format": memory_format}
+    return {}
+
+
+def _conv_bf16(conv, x, **layout):
     return ops.conv2d_bf16(x, conv.weight, None, stride=conv.stride,
-                           padding=conv.padding, out_dtype=torch.bfloat16)
+                           padding=conv.padding, out_dtype=torch.bfloat16,
+                           **layout)
 
 
-def _bn(bn, x, residual=None, fuse_relu=False):
+def _bn(bn, x, residual=None, fuse_relu=False, **layout):
     return ops.batchnorm2d(x, bn.weight, bn.bias, bn.running_mean,
                            bn.running_var, training=bn.training,
                            momentum=bn.momentum, eps=bn.eps,
-                           residual=residual, fuse_relu=fuse_relu)
+                           residual=residual, fuse_relu=fuse_relu, **layout)
 
 
 class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, in_ch, width, stride=1, downsample=None,
-                 compute_dtype: Optional[torch.dtype] = None):
+                 compute_dtype: Optional[torch.dtype] = None,
+                 memory_format=torch.contiguous_format):
         super().__init__()
         self.compute_dtype = _check_compute_dtype("Bottleneck", compute_dtype)
+        self.memory_format = _check_memory_format(
+            "Bottleneck", memory_format, compute_dtype)
         out_ch = width * self.expansion
         self.conv1 = nn.Conv2d(in_ch, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
@@ -80,14 +111,17 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def _forward_bf16(self, x):
-        out = _bn(self.bn1, _conv_bf16(self.conv1, x), fuse_relu=True)
-        out = _bn(self.bn2, _conv_bf16(self.conv2, out), fuse_relu=True)
+        mf = _layout_kw(self.memory_format)
+        out = _bn(self.bn1, _conv_bf16(self.conv1, x, **mf), fuse_relu=True,
+                  **mf)
+        out = _bn(self.bn2, _conv_bf16(self.conv2, out, **mf), fuse_relu=True,
+                  **mf)
         identity = x
         if self.downsample is not None:
             identity = _bn(self.downsample[1],
-                           _conv_bf16(self.downsample[0], x))
-        return _bn(self.bn3, _conv_bf16(self.conv3, out), residual=identity,
-                   fuse_relu=True)
+                           _conv_bf16(self.downsample[0], x, **mf), **mf)
+        return _bn(self.bn3, _conv_bf16(self.conv3, out, **mf),
+                   residual=identity, fuse_relu=True, **mf)
 
     def forward(self, x):
         if self.compute_dtype is not None:
@@ -103,9 +137,12 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes=1000,
-                 compute_dtype: Optional[torch.dtype] = None):
+                 compute_dtype: Optional[torch.dtype] = None,
+                 memory_format=torch.contiguous_format):
         super().__init__()
         self.compute_dtype = _check_compute_dtype("ResNet", compute_dtype)
+        self.memory_format = _check_memory_format(
+            "ResNet", memory_format, compute_dtype)
         self.in_ch = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -134,20 +171,24 @@ class ResNet(nn.Module):
                           bias=False),
                 nn.BatchNorm2d(out_ch))
         layers = [Bottleneck(self.in_ch, width, stride, downsample,
-                             compute_dtype=self.compute_dtype)]
+                             compute_dtype=self.compute_dtype,
+                             memory_format=self.memory_format)]
         self.in_ch = out_ch
         for _ in range(1, blocks):
             layers.append(Bottleneck(self.in_ch, width,
-                                     compute_dtype=self.compute_dtype))
+                                     compute_dtype=self.compute_dtype,
+                                     memory_format=self.memory_format))
         return nn.Sequential(*layers)
 
     def forward(self, x):
         if self.compute_dtype is not None:
-            x = _bn(self.bn1, _conv_bf16(self.conv1, x), fuse_relu=True)
+            mf = _layout_kw(self.memory_format)
+            x = _bn(self.bn1, _conv_bf16(self.conv1, x, **mf), fuse_relu=True,
+                    **mf)
             x = ops.maxpool2d(x, self.maxpool.kernel_size,
-                              self.maxpool.stride, self.maxpool.padding)
+                              self.maxpool.stride, self.maxpool.padding, **mf)
             x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-            x = ops.global_avgpool2d(x)
+            x = ops.global_avgpool2d(x, **mf)
             return ops.linear_bf16(x, self.fc.weight, self.fc.bias,
                                    out_dtype=torch.float32)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
@@ -157,5 +198,7 @@ class ResNet(nn.Module):
 
 
 def resnet50(num_classes=1000,
-             compute_dtype: Optional[torch.dtype] = None) -> ResNet:
-    return ResNet((3, 4, 6, 3), num_classes, compute_dtype=compute_dtype)
+             compute_dtype: Optional[torch.dtype] = None,
+             memory_format=torch.contiguous_format) -> ResNet:
+    return ResNet((3, 4, 6, 3), num_classes, compute_dtype=compute_dtype,
+                  memory_format=memory_format)

@@ -15,10 +15,13 @@ in ``csrc/pointwise.hip``, K16-K21 in the files named at their sections):
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
          the same on channels-last storage  -> conv2d_bf16(memory_format=
                                               torch.channels_last)
-  K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d
+  K18    batchnorm2d (+residual add, +ReLU) -> batchnorm2d (fp32, bf16)
   K19    maxpool2d (kernel, stride, padding) -> maxpool2d (fp32, bf16)
   K20    global average pool [B,C,H,W]->[B,C] -> global_avgpool2d
                                               (fp32, bf16)
+         K18-K20 on channels-last storage   -> the same three with
+                                              memory_format=
+                                              torch.channels_last
   K9+K10 log_softmax fused with NLL loss   -> log_softmax, nll_loss,
                                               log_softmax_nll
   K21    cross-entropy for wide rows (label   -> cross_entropy (fp32, bf16)
@@ -727,6 +730,25 @@ def _empty_nhwc(B, C, H, W, like, dtype):
                        dtype=dtype).permute(0, 3, 1, 2)
 
 
+def _is_nhwc(op, memory_format):
+    """True for ``torch.channels_last``, False for
+    ``torch.contiguous_format``; the layout is named, never guessed from
+    strides, so anything else is an error."""
+    if memory_format not in (torch.contiguous_format, torch.channels_last):
+        raise ValueError(f"{op}: memory_format must be "
+                         f"torch.contiguous_format or torch.channels_last, "
+                         f"got {memory_format}")
+    return memory_format == torch.channels_last
+
+
+def _laid_out(t, nhwc):
+    """``t`` in the storage the kernels of the chosen layout read.  CPU
+    tensors always run the default path's arithmetic, on NCHW storage."""
+    if t is None:
+        return None
+    return _as_nhwc(t) if nhwc and t.is_cuda else t.contiguous()
+
+
 class _Conv2dNhwcBf16(torch.autograd.Function):
     """conv2d_bf16 on channels-last storage (csrc/conv_nhwc_bf16.hip): the
     logical shapes are _Conv2dBf16's, activations lie [B][H][W][C]."""
@@ -843,10 +865,7 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
     the result and ``gx`` come back with that storage, ``gw`` dense
     [K,C,R,S].  The layout is never taken from ``x``'s strides: any other
     value than these two raises ``ValueError``."""
-    if memory_format not in (torch.contiguous_format, torch.channels_last):
-        raise ValueError(f"conv2d_bf16: memory_format must be "
-                         f"torch.contiguous_format or torch.channels_last, "
-                         f"got {memory_format}")
+    nhwc = _is_nhwc("conv2d_bf16", memory_format)
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"conv2d_bf16: out_dtype must be torch.bfloat16 or "
                         f"torch.float32, got {out_dtype}")
@@ -889,7 +908,7 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
                     ("out", B * K * OH * OW)):
         if v >= 2 ** 62:
             raise ValueError(f"conv2d_bf16: {what} has too many elements")
-    if memory_format == torch.channels_last:
+    if nhwc:
         return _Conv2dNhwcBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
     return _Conv2dBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
 
@@ -910,29 +929,46 @@ def _bn_chan(t):
 
 
 def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
-                         training, momentum, eps, residual, fuse_relu):
-    """The forward of ``batchnorm2d`` on checked, contiguous tensors.
-    Returns ``(y, save_mean, save_invstd)``: the fp32 batch statistics the
-    backward uses in training, ``(y, None, None)`` in eval."""
+                         training, momentum, eps, residual, fuse_relu,
+                         memory_format=torch.contiguous_format):
+    """The forward of ``batchnorm2d`` on checked tensors, contiguous or,
+    with ``memory_format=torch.channels_last``, brought to channels-last
+    storage here.  Returns ``(y, save_mean, save_invstd)``: the fp32 batch
+    statistics the backward uses in training, ``(y, None, None)`` in
+    eval."""
+    nhwc = _is_nhwc("ops.batchnorm2d", memory_format)
     B, C, H, W = x.shape
     if x.is_cuda:
         k = _k()
-        y = torch.empty_like(x)
         mean = invstd = ws = None
         splits = 1
+        if nhwc:
+            x, residual = _as_nhwc(x), _laid_out(residual, True)
+            y = _empty_nhwc(B, C, H, W, x, x.dtype)
+            get_splits, dims = k.batchnorm2d_nhwc_splits, (B * H * W, C)
+            fwd = k.batchnorm2d_nhwc_fwd
+        else:
+            y = torch.empty_like(x)
+            get_splits, dims = k.batchnorm2d_splits, (B, C, H * W)
+            fwd = k.batchnorm2d_fwd
         if training:
             mean = torch.empty(C, device=x.device, dtype=torch.float32)
             invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-            splits = k.batchnorm2d_splits(B, C, H * W)
+            splits = get_splits(*dims)
             ws = torch.empty(C * splits * 3, device=x.device,
                              dtype=torch.float32)
-        k.batchnorm2d_fwd(
-            x.data_ptr(), _ptr(residual), y.data_ptr(), weight.data_ptr(),
+        fwd(x.data_ptr(), _ptr(residual), y.data_ptr(), weight.data_ptr(),
             bias.data_ptr(), _ptr(running_mean), _ptr(running_var),
-            _ptr(mean), _ptr(invstd), _ptr(ws), splits, B, C, H * W,
+            _ptr(mean), _ptr(invstd), _ptr(ws), splits, *dims,
             training, momentum, eps, fuse_relu, x.dtype == torch.bfloat16,
             _stream())
         return y, mean, invstd
+    if nhwc:
+        # the default path's arithmetic, so the values are its bits
+        y, mean, invstd = _batchnorm2d_forward(
+            x.contiguous(), weight, bias, running_mean, running_var,
+            training, momentum, eps, _laid_out(residual, False), fuse_relu)
+        return _as_nhwc(y), mean, invstd
     xf = x.float()
     if training:
         n = B * H * W
@@ -959,10 +995,11 @@ def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
 class _BatchNorm2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var,
-                training, momentum, eps, fuse_relu):
+                training, momentum, eps, fuse_relu, memory_format):
         y, mean, invstd = _batchnorm2d_forward(
             x, weight, bias, running_mean, running_var, training, momentum,
-            eps, residual, fuse_relu)
+            eps, residual, fuse_relu, memory_format)
+        ctx.nhwc = memory_format == torch.channels_last
         if training:
             ctx.save_for_backward(x, weight, mean, invstd,
                                   y if fuse_relu else None)
@@ -980,24 +1017,30 @@ class _BatchNorm2d(torch.autograd.Function):
         need_r = need_r and ctx.has_residual
         B, C, H, W = x.shape
         n = B * H * W
-        gy = gy.contiguous()
+        gy = _laid_out(gy, ctx.nhwc)
         gx = gres = None
         if x.is_cuda:
             k = _k()
             gw = torch.empty(C, device=x.device, dtype=torch.float32)
             gb = torch.empty(C, device=x.device, dtype=torch.float32)
+            # x is the tensor the forward read: empty_like keeps its layout
             if need_x:
                 gx = torch.empty_like(x)     # fully written
             if need_r:
                 gres = torch.empty_like(x)
-            splits = k.batchnorm2d_splits(B, C, H * W)
+            if ctx.nhwc:
+                get_splits, dims = k.batchnorm2d_nhwc_splits, (B * H * W, C)
+                bwd = k.batchnorm2d_nhwc_bwd
+            else:
+                get_splits, dims = k.batchnorm2d_splits, (B, C, H * W)
+                bwd = k.batchnorm2d_bwd
+            splits = get_splits(*dims)
             ws = torch.empty(C * splits * 2, device=x.device,
                              dtype=torch.float32)
-            k.batchnorm2d_bwd(
-                x.data_ptr(), gy.data_ptr(), _ptr(y), weight.data_ptr(),
+            bwd(x.data_ptr(), gy.data_ptr(), _ptr(y), weight.data_ptr(),
                 mean.data_ptr(), stat.data_ptr(), gw.data_ptr(),
                 gb.data_ptr(), _ptr(gx), _ptr(gres), ws.data_ptr(), splits,
-                B, C, H * W, ctx.training, ctx.eps,
+                *dims, ctx.training, ctx.eps,
                 x.dtype == torch.bfloat16, _stream())
         else:
             inv = stat if ctx.training else 1.0 / torch.sqrt(stat + ctx.eps)
@@ -1015,13 +1058,16 @@ class _BatchNorm2d(torch.autograd.Function):
                 gx = (_bn_chan(weight * inv) * t).to(x.dtype)
             if need_r:
                 gres = g.to(x.dtype)
+            if ctx.nhwc:
+                gx = _as_nhwc(gx) if need_x else None
+                gres = _as_nhwc(gres) if need_r else None
         return (gx, gw if need_w else None, gb if need_b else None, gres,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
                 training=True, momentum=0.1, eps=1e-5, residual=None,
-                fuse_relu=False):
+                fuse_relu=False, memory_format=torch.contiguous_format):
     """``relu?(batch_norm(x) + residual?)`` over NCHW in one pass.
 
     ``x`` [B,C,H,W] is fp32 or bf16 and the result has its dtype and shape;
@@ -1036,7 +1082,16 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
     dtype, the residual's gradient in its dtype (the gradient after the
     ReLU mask, exactly) and fp32 ``gweight``/``gbias``.  Statistics and
     arithmetic are fp32 with a centred variance and one rounding per
-    element; every output is bitwise reproducible."""
+    element; every output is bitwise reproducible.
+
+    ``memory_format=torch.channels_last`` runs the same contract on
+    channels-last storage (csrc/batchnorm_nhwc.hip), with
+    ``conv2d_bf16``'s rules: ``x``, ``residual`` and, in backward, ``gy``
+    keep their logical [B,C,H,W] shape and are brought to [B][H][W][C]
+    storage, which costs nothing where they have it; ``y``, ``gx`` and the
+    residual's gradient come back with that storage.  The layout is never
+    taken from ``x``'s strides: any other value raises ``ValueError``."""
+    nhwc = _is_nhwc("ops.batchnorm2d", memory_format)
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"ops.batchnorm2d: x must be fp32 or bf16, got "
                         f"{x.dtype}")
@@ -1083,7 +1138,7 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
         if residual.device != x.device:
             raise ValueError("ops.batchnorm2d: residual is on another "
                              "device than x")
-        residual = residual.contiguous()
+        residual = _laid_out(residual, nhwc)
     if momentum is None:
         raise ValueError("ops.batchnorm2d: momentum=None (cumulative moving "
                          "average) is not supported; pass a float in [0, 1]")
@@ -1103,9 +1158,9 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
         raise ValueError("ops.batchnorm2d: training=False needs "
                          "running_mean and running_var")
     return _BatchNorm2d.apply(
-        x.contiguous(), weight.contiguous(), bias.contiguous(), residual,
+        _laid_out(x, nhwc), weight.contiguous(), bias.contiguous(), residual,
         running_mean, running_var, bool(training), float(momentum),
-        float(eps), bool(fuse_relu))
+        float(eps), bool(fuse_relu), memory_format)
 
 
 # ---------------------------------------------------------------------------
@@ -1138,45 +1193,57 @@ def _check_pool_input(op, x):
 
 class _MaxPool2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, kernel, stride, padding):
+    def forward(ctx, x, kernel, stride, padding, nhwc):
         B, C, H, W = x.shape
         (kh, kw), (sh, sw), (ph, pw) = kernel, stride, padding
         ctx.geom = (B, C, H, W, kh, kw, sh, sw, ph, pw)
+        ctx.nhwc = nhwc
         if x.is_cuda:
             OH = (H + 2 * ph - kh) // sh + 1
             OW = (W + 2 * pw - kw) // sw + 1
-            y = torch.empty(B, C, OH, OW, device=x.device, dtype=x.dtype)
-            slot = torch.empty(B, C, OH, OW, device=x.device,
-                               dtype=torch.uint8)
-            _k().maxpool2d_fwd(x.data_ptr(), y.data_ptr(), slot.data_ptr(),
-                               *ctx.geom, x.dtype == torch.bfloat16,
-                               _stream())
+            if nhwc:    # y and the slots both lie [B][OH][OW][C]
+                y = _empty_nhwc(B, C, OH, OW, x, x.dtype)
+                slot = _empty_nhwc(B, C, OH, OW, x, torch.uint8)
+                fwd = _k().maxpool2d_nhwc_fwd
+            else:
+                y = torch.empty(B, C, OH, OW, device=x.device, dtype=x.dtype)
+                slot = torch.empty(B, C, OH, OW, device=x.device,
+                                   dtype=torch.uint8)
+                fwd = _k().maxpool2d_fwd
+            fwd(x.data_ptr(), y.data_ptr(), slot.data_ptr(), *ctx.geom,
+                x.dtype == torch.bfloat16, _stream())
             ctx.save_for_backward(slot)
             return y
         y, idx = F.max_pool2d(x, kernel, stride, padding,
                               return_indices=True)
         ctx.save_for_backward(idx)
-        return y
+        return _as_nhwc(y) if nhwc else y
 
     @staticmethod
     def backward(ctx, gy):
         (saved,) = ctx.saved_tensors
         B, C, H, W = ctx.geom[:4]
-        gy = gy.contiguous()
+        gy = _laid_out(gy, ctx.nhwc)
         if gy.is_cuda:
-            gx = torch.empty(B, C, H, W, device=gy.device,
-                             dtype=gy.dtype)      # fully written
-            _k().maxpool2d_bwd(gy.data_ptr(), saved.data_ptr(),
-                               gx.data_ptr(), *ctx.geom,
-                               gy.dtype == torch.bfloat16, _stream())
-            return gx, None, None, None
+            if ctx.nhwc:
+                gx = _empty_nhwc(B, C, H, W, gy, gy.dtype)  # fully written
+                bwd = _k().maxpool2d_nhwc_bwd
+            else:
+                gx = torch.empty(B, C, H, W, device=gy.device,
+                                 dtype=gy.dtype)      # fully written
+                bwd = _k().maxpool2d_bwd
+            bwd(gy.data_ptr(), saved.data_ptr(), gx.data_ptr(), *ctx.geom,
+                gy.dtype == torch.bfloat16, _stream())
+            return gx, None, None, None, None
         gx = torch.zeros(B * C, H * W, dtype=torch.float32)
         gx.scatter_add_(1, saved.reshape(B * C, -1),
                         gy.float().reshape(B * C, -1))
-        return gx.to(gy.dtype).view(B, C, H, W), None, None, None
+        gx = gx.to(gy.dtype).view(B, C, H, W)
+        return _as_nhwc(gx) if ctx.nhwc else gx, None, None, None, None
 
 
-def maxpool2d(x, kernel_size, stride=None, padding=0):
+def maxpool2d(x, kernel_size, stride=None, padding=0,
+              memory_format=torch.contiguous_format):
     """``max_pool2d(x, kernel_size, stride, padding)`` over NCHW.
 
     ``x`` [B,C,H,W] is fp32 or bf16 and the result [B,C,OH,OW] has its
@@ -1192,8 +1259,14 @@ def maxpool2d(x, kernel_size, stride=None, padding=0):
     Backward gives ``gx`` in ``x``'s dtype: per input element the fp32 sum,
     in a fixed order, of the gradients of the windows that selected it,
     rounded once, and exact zeros elsewhere.  No atomics are used, so the
-    gradient of overlapping windows is bitwise reproducible."""
+    gradient of overlapping windows is bitwise reproducible.
+
+    ``memory_format=torch.channels_last`` (``conv2d_bf16``'s rules) runs
+    csrc/pool_nhwc.hip on [B][H][W][C] storage: ``x`` and ``gy`` are brought
+    to it at no cost where they have it, ``y`` and ``gx`` come back with
+    it, and every element is the default layout's, bit for bit."""
     op = "ops.maxpool2d"
+    nhwc = _is_nhwc(op, memory_format)
     _check_pool_input("maxpool2d", x)
     kh, kw = _pair(kernel_size, "kernel_size", 1, op)
     sh, sw = (kh, kw) if stride is None else _pair(stride, "stride", 1, op)
@@ -1212,7 +1285,8 @@ def maxpool2d(x, kernel_size, stride=None, padding=0):
     if max(sh, sw) > _POOL_MAX_PLANE:
         raise ValueError(f"{op}: stride {(sh, sw)} does not fit the "
                          f"kernel's 32-bit index")
-    return _MaxPool2d.apply(x.contiguous(), (kh, kw), (sh, sw), (ph, pw))
+    return _MaxPool2d.apply(_laid_out(x, nhwc), (kh, kw), (sh, sw), (ph, pw),
+                            nhwc)
 
 
 # ---------------------------------------------------------------------------
@@ -1224,14 +1298,20 @@ def maxpool2d(x, kernel_size, stride=None, padding=0):
 # ---------------------------------------------------------------------------
 class _GlobalAvgPool2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, nhwc):
         B, C, H, W = x.shape
         ctx.in_shape = (B, C, H, W)
+        ctx.nhwc = nhwc
         if x.is_cuda:
             y = torch.empty(B, C, device=x.device, dtype=x.dtype)
-            _k().global_avgpool2d_fwd(x.data_ptr(), y.data_ptr(), B * C,
-                                      H * W, x.dtype == torch.bfloat16,
-                                      _stream())
+            if nhwc:
+                _k().global_avgpool2d_nhwc_fwd(
+                    x.data_ptr(), y.data_ptr(), B, C, H * W,
+                    x.dtype == torch.bfloat16, _stream())
+            else:
+                _k().global_avgpool2d_fwd(x.data_ptr(), y.data_ptr(), B * C,
+                                          H * W, x.dtype == torch.bfloat16,
+                                          _stream())
             return y
         return (x.float().sum(dim=(2, 3)) / (H * W)).to(x.dtype)
 
@@ -1240,17 +1320,24 @@ class _GlobalAvgPool2d(torch.autograd.Function):
         B, C, H, W = ctx.in_shape
         gy = gy.contiguous()
         if gy.is_cuda:
+            if ctx.nhwc:
+                gx = _empty_nhwc(B, C, H, W, gy, gy.dtype)  # fully written
+                _k().global_avgpool2d_nhwc_bwd(
+                    gy.data_ptr(), gx.data_ptr(), B, C, H * W,
+                    gy.dtype == torch.bfloat16, _stream())
+                return gx, None
             gx = torch.empty(B, C, H, W, device=gy.device,
                              dtype=gy.dtype)      # fully written
             _k().global_avgpool2d_bwd(gy.data_ptr(), gx.data_ptr(), B * C,
                                       H * W, gy.dtype == torch.bfloat16,
                                       _stream())
-            return gx
+            return gx, None
         g = (gy.float() / (H * W)).to(gy.dtype)
-        return g.view(B, C, 1, 1).expand(B, C, H, W).contiguous()
+        gx = g.view(B, C, 1, 1).expand(B, C, H, W)
+        return _as_nhwc(gx) if ctx.nhwc else gx.contiguous(), None
 
 
-def global_avgpool2d(x):
+def global_avgpool2d(x, memory_format=torch.contiguous_format):
     """The mean of every plane: ``adaptive_avg_pool2d(x, 1).flatten(1)``.
 
     ``x`` [B,C,H,W] is fp32 or bf16; the result is [B,C] in its dtype.
@@ -1259,9 +1346,16 @@ def global_avgpool2d(x):
     bitwise reproducible, a view at any element offset gives the bits of
     its aligned copy, and the bf16 result is the fp32 op's on the same
     values, rounded once.  Backward gives ``gx[b,c,:,:] = gy[b,c] / (H*W)``
-    in ``x``'s dtype, computed in fp32 and rounded once."""
+    in ``x``'s dtype, computed in fp32 and rounded once.
+
+    ``memory_format=torch.channels_last`` (``conv2d_bf16``'s rules) runs
+    csrc/pool_nhwc.hip on [B][H][W][C] storage, which ``x`` is brought to at
+    no cost where it has it; the result is still a dense [B,C] and ``gx``
+    comes back channels-last.  The order of the sum is again fixed by
+    ``H*W`` alone, but it is another order than the default layout's."""
+    nhwc = _is_nhwc("ops.global_avgpool2d", memory_format)
     _check_pool_input("global_avgpool2d", x)
-    return _GlobalAvgPool2d.apply(x.contiguous())
+    return _GlobalAvgPool2d.apply(_laid_out(x, nhwc), nhwc)
 
 
 # ---------------------------------------------------------------------------
