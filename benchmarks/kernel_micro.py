@@ -95,10 +95,10 @@ def main():
 
     # the forward alone (loss_part mode, no prologue dispatch): the tiled
     # kernel and the 256-thread one, one and two workgroups per sample
-    def fwd_raw(tiled, split):
+    def fwd_raw(tiled, split, gl=0):
         return lambda: k.net_fwd_raw(
             x.data_ptr(), pp, tgt.data_ptr(), ws.ptrs, _seed_ptr(dev), B,
-            True, tiled, split, 60000, s)
+            True, tiled, split, 60000, s, gl)
 
     for tiled in (True, False):
         for sp in (1, 2):
@@ -106,6 +106,9 @@ def main():
                 continue
             name = "tiled" if tiled else "old"
             results[f"fwd {name} (split={sp})"] = time_fn(fwd_raw(tiled, sp))
+            if tiled:   # with the head of the data backward (step paths)
+                results[f"fwd tiled+head (split={sp})"] = time_fn(
+                    fwd_raw(tiled, sp, ws["one"].data_ptr()))
     # full bwd+gw+combine bundle is what bwd() launches; time the pieces
     for sp in (1, 2, 4, 8):
         os.environ["DTP_BWD_SPLIT"] = str(sp)
@@ -114,19 +117,25 @@ def main():
 
     # the data backward alone, both kernels (DTP_BWD_TILED=0: the
     # 256-thread strip loop) at each sibling split; "auto" is the default
-    def bwd_data():
+    def bwd_data(head_done=False):
         k.net_bwd_data_raw(pp[2], pp[4], pp[6], tgt.data_ptr(),
-                           ws["one"].data_ptr(), ws.ptrs, B, True, s)
+                           ws["one"].data_ptr(), ws.ptrs, B, True, s,
+                           head_done)
 
-    for tiled in (1, 0):
-        os.environ["DTP_BWD_TILED"] = str(tiled)
+    # "tiled from ga2": the tiled kernel without the head, starting from
+    # the ga2 that a forward with the head left in the workspace (the step
+    # paths' default)
+    fwd_raw(True, 1, ws["one"].data_ptr())()
+    for tiled in (2, 1, 0):
+        os.environ["DTP_BWD_TILED"] = str(min(tiled, 1))
         for sp in ("auto", 1, 2, 4, 8):
             if sp == "auto":
                 os.environ.pop("DTP_BWD_SPLIT", None)
             else:
                 os.environ["DTP_BWD_SPLIT"] = str(sp)
-            name = "tiled" if tiled else "strip"
-            results[f"bwd data {name} (split={sp})"] = time_fn(bwd_data)
+            name = ("strip", "tiled", "tiled from ga2")[tiled]
+            results[f"bwd data {name} (split={sp})"] = time_fn(
+                lambda: bwd_data(tiled == 2))
     os.environ.pop("DTP_BWD_SPLIT", None)
     os.environ.pop("DTP_BWD_TILED", None)
     base = 0
@@ -143,7 +152,7 @@ def main():
     results["sgd"] = time_fn(opt.step)
 
     for name, us in results.items():
-        print(f"{name:24s} {us:8.2f} us")
+        print(f"{name:36s} {us:8.2f} us")
 
 
 if __name__ == "__main__":

@@ -25,6 +25,14 @@ BWD = ["w2 staging", "g_logits", "g_h1", "g_p2 (wf1)", "tile zero+scatter",
        "ga2 stash", "conv2 bwd_x FMAs", "k-group sum + pool1 bwd"]
 FWD = ["staging", "conv1+pool1", "conv2+pool2", "sibling hand-off", "fc1",
        "fc2+softmax"]
+# with the head of the data backward in the tiled forward (the default of
+# the step paths): the forward goes on through stamps 16..18, the tiled
+# backward is stamps 0, 1, 19, 7, 8
+FWD_HEAD = FWD + ["g_logits", "g_h1", "g_p2 + ga2 write"]
+FWD_HEAD_COLS = list(range(9, 16)) + [16, 17, 18]
+BWD_NOHEAD = ["w2 staging + ring zero", "ga2 tile load", "conv2 bwd_x FMAs",
+              "k-group sum + pool1 bwd"]
+BWD_NOHEAD_COLS = [0, 1, 19, 7, 8]
 
 
 def load_stamped():
@@ -40,14 +48,15 @@ def load_stamped():
     return mod
 
 
-def shares(st, lo, names, title):
-    """st: [blocks, NSTAMP] int64; stages are consecutive stamps from lo.
+def shares(st, lo, names, title, which=None):
+    """st: [blocks, NSTAMP] int64; stages are consecutive stamps from lo,
+    or the stamps listed in `which`.
     Only workgroups that passed every boundary count (a forward sibling 1
     leaves after the hand-off; the strip kernel has no stamp 7)."""
     hi = lo + len(names)
-    cols = st[:, lo:hi + 1]
+    cols = st[:, lo:hi + 1] if which is None else st[:, which]
     full = (cols != 0).all(dim=1)
-    if not bool(full.any()):      # the strip loop: fold stamps 7 into 8
+    if which is None and not bool(full.any()):  # strip loop: fold 7 into 8
         keep = [i for i in range(lo, hi + 1) if i != 7]
         cols, names = st[:, keep], names[:-2] + ["conv2 bwd_x + pool1 bwd"]
         full = (cols != 0).all(dim=1)
@@ -75,6 +84,19 @@ def main():
     x = torch.randn(B, 1, 28, 28, device=dev)
     tgt = torch.randint(0, 10, (B,), device=dev)
     n = k.STAGE_NSTAMP
+    # the default first: head in the forward, the backward starts from ga2
+    os.environ.pop("DTP_HEAD_IN_FWD", None)
+    for _ in range(20):
+        net_fused_step(net, x, tgt)
+    k.stage_stamps_clear()
+    net_fused_step(net, x, tgt)
+    st = torch.tensor(k.stage_stamps(), dtype=torch.int64).view(-1, n)
+    shares(st, 0, BWD_NOHEAD, f"data backward, B={B}, tiled kernel, head "
+           "in the forward", BWD_NOHEAD_COLS)
+    shares(st, 9, FWD_HEAD, f"forward, B={B}, tiled kernel with the head",
+           FWD_HEAD_COLS)
+    # then every kernel with the head where it used to be
+    os.environ["DTP_HEAD_IN_FWD"] = "0"
     for tiled in ("1", "0"):
         os.environ["DTP_BWD_TILED"] = tiled
         for _ in range(20):
@@ -95,6 +117,7 @@ def main():
         shares(st, 9, FWD, f"forward, B={B}, "
                + ("tiled kernel" if tiled == "1" else "256-thread kernel"))
     os.environ.pop("DTP_FWD_TILED", None)
+    os.environ.pop("DTP_HEAD_IN_FWD", None)
 
 
 if __name__ == "__main__":

@@ -119,11 +119,15 @@ __global__ void step_prologue_kernel(unsigned long long* s, float* loss) {
 // perturb the kernels, so lengths are not to be quoted).
 //   bwd: 0 entry, 1 w2 staged + sample start, 2 g_logits, 3 g_h1, 4 g_p2,
 //        5 tile zeroed + scattered, 6 ga2 stashed (head done),
-//        7 conv2-bwd_x partials done, 8 sample done
+//        7 conv2-bwd_x partials done, 8 sample done;
+//        without the head (it ran in the forward): 0, 1, then 19 ga2
+//        loaded into the tile, 7, 8
 //   fwd: 9 entry, 10 x/w staged, 11 conv1+pool1, 12 conv2+pool2,
-//        13 sibling hand-off done, 14 fc1, 15 fc2+softmax (sample done)
+//        13 sibling hand-off done, 14 fc1, 15 fc2+softmax (sample done);
+//        with the head of the data backward: 16 g_logits, 17 g_h1,
+//        18 g_p2 + ga2 written
 #ifdef DTP_STAGE_STAMPS
-#define STAGE_NSTAMP 16
+#define STAGE_NSTAMP 20
 #define STAGE_NBLK 4096
 __device__ unsigned long long g_stage_stamps[STAGE_NBLK * STAGE_NSTAMP];
 #define STAGE_STAMP(i)                                                   \
@@ -136,21 +140,23 @@ __device__ unsigned long long g_stage_stamps[STAGE_NBLK * STAGE_NSTAMP];
 #define STAGE_STAMP(i) do {} while (0)
 #endif
 
-// p2 access of the split forward's sibling hand-off.  ON: a relaxed
+// p2 (float) and pool2 index-byte (uint8_t, tiled forward only) access of
+// the split forward's sibling hand-off.  ON: a relaxed
 // agent-scope (sc1) store or load, which goes to the device's coherence
 // point, so sibling 1's p2 half is visible to sibling 0 on another CU
 // once the stores have retired and the flag is written after them: no
 // fence, hence no cache writeback or invalidate under the workgroups
 // that run beside them.  The store is shared with the unsplit forward,
 // where it is a plain store (ON false); only sibling 0 loads.
-template <bool ON>
-__device__ __forceinline__ void sc1_st(float* p, float v) {
+template <bool ON, typename T>
+__device__ __forceinline__ void sc1_st(T* p, T v) {
   if (ON)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else
     *p = v;
 }
-__device__ __forceinline__ float sc1_ld(const float* p) {
+template <typename T>
+__device__ __forceinline__ T sc1_ld(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -558,7 +564,14 @@ net_fused_fwd_split_kernel(
 //    stride 28 with the (k, c) slot as the lane index, p1 plane stride
 //    148 (37 quads, odd: ten channels land on ten bank quads; the
 //    natural 144 puts all of them on the same four).
-//  - fc1: 8 lanes per output on 400 lanes, ten float4 of wf1 per lane.
+//  - fc1: 8 lanes per output on 400 lanes, ten float4 of wf1 per lane,
+//    loaded (with bf1 and, split kernel, fc2's weights) ahead of the
+//    hand-off, whose poll covers the round trip.
+//  - gl given (the step paths): sibling 0 also runs the head of the data
+//    backward after the softmax, net_bwd_head's arithmetic on what is
+//    still in LDS, and writes glog / gh1 / the dense ga2; the backward
+//    (net_fused_bwd_tiled_nohead_kernel) then starts from ga2.  For that
+//    it needs the pool2 index bytes of both halves: they travel with p2.
 #define FT_NT 512    // threads
 #define FT_WS 28     // staged filter stride
 #define FT_PS 148    // p1 plane stride
@@ -633,7 +646,10 @@ net_fused_fwd_tiled_kernel(
     float* __restrict__ loss_part,
     const unsigned long long* __restrict__ seed_p,
     int B, int training, unsigned int* __restrict__ flags,
-    unsigned int token, int poll_bound) {
+    unsigned int token, int poll_bound,
+    const float* __restrict__ gl,      // dLoss (device scalar), or null
+    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
+    float* __restrict__ ga2_ws) {
   constexpr int KL = SPLIT ? N_C2K / 2 : N_C2K;  // conv2 channels here
   constexpr int NG = SPLIT ? 10 : 5;             // input-channel groups
   constexpr int CPG = N_C1K / NG;                // channels per group
@@ -649,11 +665,26 @@ net_fused_fwd_tiled_kernel(
   __shared__ float d3[N_H1];
   __shared__ float logits[N_CLS];
   __shared__ unsigned s_got;
+  // the head of the data backward (gl given): g_logits, g_h1, and what it
+  // reads of this sample's forward, the pool2 index bytes of all 320
+  // cells and per fc1 output bit 0 dropout keep, bit 1 ReLU alive
+  __shared__ float glg[N_CLS];
+  __shared__ float gh1s[N_H1];
+  __shared__ uint8_t idxs[N_P2];
+  __shared__ uint8_t hks[N_H1];
   const int tid = threadIdx.x;
   const uint64_t seed = seed_p[0];
   // split: blockIdx = 2b + half, the grid is exactly 2B
   const int half = SPLIT ? (blockIdx.x & 1) : 0;
   const int k0 = half * KL;
+  const bool head = gl != nullptr;
+  const float sc = head ? gl[0] / B : 0.f;
+  // a pointer made opaque by an empty asm (below) is global by cast: the
+  // compiler no longer knows, and flat loads would count against the LDS
+  // waits as well
+  typedef const __attribute__((address_space(1))) float* gptr_t;
+  typedef float f32x4_t __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(1))) f32x4_t* gptr4_t;
 
   STAGE_STAMP(9);
   // the weights are staged once per workgroup: w1 as [c][28], w2 as
@@ -678,6 +709,9 @@ net_fused_fwd_tiled_kernel(
     if (tid < 196)
       reinterpret_cast<float4*>(xs)[tid] =
           reinterpret_cast<const float4*>(x + (int64_t)b * 784)[tid];
+    // (read here so that neither the softmax lane nor the head's
+    // g_logits waits for it behind a barrier)
+    const int t_b = (int)tgt[b];
     __syncthreads();
     STAGE_STAMP(10);
 
@@ -771,8 +805,9 @@ net_fused_fwd_tiled_kernel(
       const uint8_t ib = ft_pool(v[0], v[1], v[2], v[3], o);
       const int i = k0 * 16 + tid;
       p2[i] = o;
+      idxs[i] = ib;
       sc1_st<SPLIT>(p2_ws + (int64_t)b * N_P2 + i, o);
-      idx2_ws[(int64_t)b * N_P2 + i] = ib;
+      sc1_st<SPLIT>(idx2_ws + (int64_t)b * N_P2 + i, ib);
     }
     if ((!SPLIT || half == 0) && training && tid < N_C2K) {
       const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + tid);
@@ -792,6 +827,33 @@ net_fused_fwd_tiled_kernel(
       }
       return;  // fc/softmax belong to sibling 0
     }
+    // fc1's weights (ten float4 of wf1 per lane, and the bias) are loaded
+    // here, ahead of the hand-off, whose poll covers their round trip.
+    // The pointer is opaque per sample so that the loads are not hoisted
+    // out of the sample loop (registers).
+    f32x4_t wv[10];
+    float bf1v = 0.f;
+    if (tid < N_H1 * 8) {
+      const float* wf1_b = wf1;
+      asm volatile("" : "+s"(wf1_b));
+      const gptr4_t wr =
+          (gptr4_t)(wf1_b + (tid >> 3) * N_P2 + (tid & 7) * 40);
+      #pragma unroll
+      for (int j = 0; j < 10; ++j) wv[j] = wr[j];
+      bf1v = bf1[tid >> 3];
+    }
+    // fc2's row of wf2 and its bias ride along where there are registers
+    // for them (the split kernel); the unsplit one loads them in fc2
+    constexpr bool W2_EARLY = SPLIT;
+    float w2r[N_H1], bf2v = 0.f;
+    if (W2_EARLY && tid < N_CLS) {
+      const float* wf2_b = wf2;
+      asm volatile("" : "+s"(wf2_b));
+      const gptr_t wr = (gptr_t)(wf2_b + tid * N_H1);
+      #pragma unroll
+      for (int kk = 0; kk < N_H1; ++kk) w2r[kk] = wr[kk];
+      bf2v = bf2[tid];
+    }
     if (SPLIT) {
       if (tid == 0) {
         unsigned got = 0;
@@ -810,9 +872,15 @@ net_fused_fwd_tiled_kernel(
       }
       __syncthreads();
       if (s_got) {
-        if (tid < N_P2 / 2)
-          p2[N_P2 / 2 + tid] =
-              sc1_ld(p2_ws + (int64_t)b * N_P2 + N_P2 / 2 + tid);
+        if (tid < N_P2 / 2) {
+          // (the index bytes ride in the same round trip; only the head
+          // reads them)
+          const int64_t o = (int64_t)b * N_P2 + N_P2 / 2 + tid;
+          const float pv = sc1_ld(p2_ws + o);
+          const uint8_t iv = sc1_ld(idx2_ws + o);
+          p2[N_P2 / 2 + tid] = pv;
+          idxs[N_P2 / 2 + tid] = iv;
+        }
       } else if (tid < N_P2 / 2) {
         // the sibling is not resident yet: its channels from our own p1
         // and w2 in global memory, one pooled cell per thread (cold, so
@@ -858,26 +926,17 @@ net_fused_fwd_tiled_kernel(
           v[0] *= dsc; v[1] *= dsc; v[2] *= dsc; v[3] *= dsc;
         }
         float o;
-        ft_pool(v[0], v[1], v[2], v[3], o);
+        idxs[i] = ft_pool(v[0], v[1], v[2], v[3], o);
         p2[i] = o;
       }
       __syncthreads();
     }
     STAGE_STAMP(13);
 
-    // fc1 (320->50) + relu + dropout: 8 lanes per output, shfl reduce.
-    // The pointer is opaque per sample so that the ten wf1 loads are not
-    // hoisted out of the sample loop (registers).
+    // fc1 (320->50) + relu + dropout: 8 lanes per output, shfl reduce
     if (tid < N_H1 * 8) {
       const int n = tid >> 3, q8 = tid & 7;
-      const float* wf1_b = wf1;
-      asm volatile("" : "+s"(wf1_b));
-      const float4* wr =
-          reinterpret_cast<const float4*>(wf1_b + n * N_P2 + q8 * 40);
       const float4* pr = reinterpret_cast<const float4*>(p2 + q8 * 40);
-      float4 wv[10];
-      #pragma unroll
-      for (int j = 0; j < 10; ++j) wv[j] = wr[j];
       float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
       #pragma unroll
       for (int j = 0; j < 10; ++j) {
@@ -892,7 +951,7 @@ net_fused_fwd_tiled_kernel(
       acc += __shfl_down(acc, 2, 8);
       acc += __shfl_down(acc, 4, 8);
       if (q8 == 0) {
-        float h = acc + bf1[n];
+        float h = acc + bf1v;
         h = h > 0.f ? h : 0.f;
         h1_ws[(int64_t)b * N_H1 + n] = h;
         float dd = h;
@@ -906,6 +965,7 @@ net_fused_fwd_tiled_kernel(
         m3_ws[(int64_t)b * N_H1 + n] = keep;
         d3_ws[(int64_t)b * N_H1 + n] = dd;
         d3[n] = dd;
+        hks[n] = (uint8_t)(keep | (h > 0.f ? 2 : 0));
       }
     }
     __syncthreads();
@@ -913,11 +973,46 @@ net_fused_fwd_tiled_kernel(
 
     // fc2 (50->10), then log_softmax + NLL on one lane, as net_fwd_sample
     if (tid < N_CLS) {
-      const float* wr = wf2 + tid * N_H1;
-      float acc = bf2[tid];
-      #pragma unroll 10
-      for (int kk = 0; kk < N_H1; ++kk) acc += d3[kk] * wr[kk];
+      float acc;
+      if (W2_EARLY) {
+        // (explicit FMAs: the loop below compiles to one FMA chain, and
+        // written as `+=` this unrolled form is vectorized into packed
+        // multiplies and adds instead, which moves the logits an ulp)
+        acc = bf2v;
+        #pragma unroll
+        for (int kk = 0; kk < N_H1; ++kk) acc = fmaf(d3[kk], w2r[kk], acc);
+      } else {
+        const float* wr = wf2 + tid * N_H1;
+        acc = bf2[tid];
+        #pragma unroll 10
+        for (int kk = 0; kk < N_H1; ++kk) acc += d3[kk] * wr[kk];
+      }
       logits[tid] = acc;
+    }
+    // head: lane i of 320 needs column i of wf1 (50 floats, L2-hot) for
+    // g_p2, lane n of 50 column n of wf2 for g_h1.  The split kernel has
+    // the registers to issue these loads here, behind fc2's own (loads
+    // return in order: ahead of them they made fc2 wait), so that the
+    // softmax and g_logits cover their round trip; the unsplit one (at the
+    // VGPR limit) loads them where they are used.  Opaque per sample, as
+    // in fc1: hoisted out of the sample loop the values would stay live
+    // through both conv stages.
+    constexpr bool WT_EARLY = SPLIT;
+    const float* wf1_o = wf1;
+    const float* wf2_o = wf2;
+    asm volatile("" : "+s"(wf1_o), "+s"(wf2_o));
+    const gptr_t wf1_h = (gptr_t)wf1_o;
+    const gptr_t wf2_h = (gptr_t)wf2_o;
+    float wt[N_H1], w2t[N_CLS];
+    if (WT_EARLY && head) {
+      if (tid < N_H1) {
+        #pragma unroll
+        for (int n = 0; n < N_CLS; ++n) w2t[n] = wf2_h[n * N_H1 + tid];
+      }
+      if (tid < N_P2) {
+        #pragma unroll
+        for (int n = 0; n < N_H1; ++n) wt[n] = wf1_h[n * N_P2 + tid];
+      }
     }
     __syncthreads();
     if (tid == 0) {
@@ -929,17 +1024,92 @@ net_fused_fwd_tiled_kernel(
       for (int i = 0; i < N_CLS; ++i) ssum += __expf(logits[i] - m);
       const float lse = m + __logf(ssum);
       float lp_t = 0.f;
-      const int64_t t = tgt[b];
       #pragma unroll
       for (int i = 0; i < N_CLS; ++i) {
         const float lp = logits[i] - lse;
         logp_ws[(int64_t)b * N_CLS + i] = lp;
-        if (i == (int)t) lp_t = lp;
+        if (head) logits[i] = lp;  // the head starts from the log-probs
+        if (i == t_b) lp_t = lp;
       }
       lsum += -lp_t / B;
     }
     __syncthreads();
     STAGE_STAMP(15);
+
+    // The head of this sample's data backward (step paths: the loss
+    // gradient is known before the forward runs).  net_bwd_head's
+    // expressions and summation orders on the values that are still in
+    // LDS; the data-backward kernel then starts from ga2.
+    if (head) {
+      // g_logits = (exp(logp) - onehot) * gl / B
+      if (tid < N_CLS) {
+        const float g = (__expf(logits[tid]) -
+                         (tid == t_b ? 1.f : 0.f)) * sc;
+        glg[tid] = g;
+        glog_ws[(int64_t)b * N_CLS + tid] = g;
+      }
+      __syncthreads();
+      STAGE_STAMP(16);
+      // g_d3 = wf2^T g_logits ; through dropout + relu -> g_h1pre
+      if (tid < N_H1) {
+        // each product rounded, then added (contraction off): in
+        // net_bwd_head these ten terms compile to packed multiplies and
+        // separate adds, here the compiler would fuse them into FMAs and
+        // gh1 would differ from the backward's in the last bit
+        if (!WT_EARLY) {
+          #pragma unroll
+          for (int n = 0; n < N_CLS; ++n) w2t[n] = wf2_h[n * N_H1 + tid];
+        }
+        float acc = 0.f;
+        {
+          #pragma clang fp contract(off)
+          #pragma unroll
+          for (int n = 0; n < N_CLS; ++n) acc += w2t[n] * glg[n];
+        }
+        float g = acc;
+        const uint8_t hk = hks[tid];
+        if (training) g = (hk & 1) ? g * 2.f : 0.f;
+        if (!(hk & 2)) g = 0.f;
+        gh1s[tid] = g;
+        gh1_ws[(int64_t)b * N_H1 + tid] = g;
+      }
+      __syncthreads();
+      STAGE_STAMP(17);
+      // g_p2 = wf1^T g_h1pre in four chains, then pool2 bwd + dropout2d
+      // bwd: the lane owns its cell's 2x2 window of ga2, so all of
+      // ga2_ws[b] is written (three or four exact zeros per window)
+      if (tid < N_P2) {
+        if (!WT_EARLY) {
+          #pragma unroll
+          for (int n = 0; n < N_H1; ++n) wt[n] = wf1_h[n * N_P2 + tid];
+        }
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        #pragma unroll
+        for (int n = 0; n < 48; n += 4) {
+          a0 += wt[n] * gh1s[n];
+          a1 += wt[n + 1] * gh1s[n + 1];
+          a2 += wt[n + 2] * gh1s[n + 2];
+          a3 += wt[n + 3] * gh1s[n + 3];
+        }
+        a0 += wt[48] * gh1s[48];
+        a1 += wt[49] * gh1s[49];
+        float g = (a0 + a1) + (a2 + a3);
+        const int k = tid >> 4, ph = (tid >> 2) & 3, pw = tid & 3;
+        if (training) {
+          const uint32_t rr = mix32(seed, (uint64_t)b * N_C2K + k);
+          g = (rr >= 0x80000000u) ? g * 2.f : 0.f;
+        }
+        const uint8_t v = idxs[tid];
+        const int am = v & 3;
+        if (v & 4) g = 0.f;
+        float* gp = ga2_ws + (int64_t)b * N_A2 + k * 64 + ph * 16 + pw * 2;
+        *reinterpret_cast<float2*>(gp) =
+            make_float2(am == 0 ? g : 0.f, am == 1 ? g : 0.f);
+        *reinterpret_cast<float2*>(gp + 8) =
+            make_float2(am == 2 ? g : 0.f, am == 3 ? g : 0.f);
+      }
+      STAGE_STAMP(18);
+    }
   }
   if (tid == 0) {
     if (loss_part) loss_part[blockIdx.x] = lsum;
@@ -953,6 +1123,11 @@ net_fused_fwd_tiled_kernel(
 // NT-thread workgroup.  Every sibling of a sample recomputes it (~35k
 // FMA); sibling 0 also writes glog / gh1 / ga2 for the weight-gradient
 // pass.  Ends on a barrier: the tile is complete for all threads.
+// Runs in the strip kernel, the fwd+bwd and single-launch kernels and, on
+// the autograd path (a real upstream gradient, known only after the
+// forward), in the tiled kernel.  In the step paths the tiled forward
+// runs these stages itself, in the same order on the same values (its
+// `head` mode), and net_fused_bwd_tiled_nohead_kernel starts from ga2.
 template <int NT, int RS, int PS>
 __device__ __forceinline__ void net_bwd_head(
     int b, int half, int tid, int training, float sc,
@@ -1217,29 +1392,41 @@ static_assert(BT_ROUND * BT_KG <= BT_NT, "one item per thread per round");
 static_assert(BT_RS % 4 == 0 && BT_PS % 4 == 0 && BT_WS % 4 == 0 &&
               BT_PS >= 16 * BT_RS && BT_WS >= 25, "aligned float4 reads");
 
-__global__ void
-__launch_bounds__(BT_NT)
-net_fused_bwd_tiled_kernel(
-    const float* __restrict__ w2, const float* __restrict__ wf1,
-    const float* __restrict__ wf2,
-    const int64_t* __restrict__ tgt,
-    const float* __restrict__ gl,      // dLoss (device scalar)
-    const uint8_t* __restrict__ idx1_ws,
-    const uint8_t* __restrict__ m2_ws,
-    const uint8_t* __restrict__ idx2_ws,
-    const float* __restrict__ h1_ws,
-    const uint8_t* __restrict__ m3_ws,
-    const float* __restrict__ logp_ws,
-    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,
-    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,
-    int B, int training, int split) {
-  __shared__ __attribute__((aligned(16))) float w2p[N_C2K * N_C1K * BT_WS];
-  __shared__ __attribute__((aligned(16))) float gd2p[N_C2K * BT_PS];
-  __shared__ __attribute__((aligned(16))) float part[BT_ROUND * BT_KG * 8];
-  __shared__ float glg[N_CLS];
-  __shared__ float gd3[N_H1];
-  __shared__ float gh1[N_H1];
-  __shared__ float gp2[N_P2];
+//  - HEAD false, net_fused_bwd_tiled_nohead_kernel (the step paths, when
+//    the tiled forward has run the head and written glog / gh1 / ga2): no
+//    head here.  The tile's zero ring is
+//    written once per workgroup; a sample's dense ga2 goes into the
+//    interior as 320 float4, the first sample's loads issued ahead of the
+//    w2 staging so that the two share one round trip.  Of the workspace
+//    it reads ga2 and idx1 only, and none of the head's LDS exists.
+//    The two variants are two plain kernels around one body, each with its
+//    own LDS: as instantiations of a kernel template their LDS arrays
+//    would be linkonce symbols, which the compiler may not drop (gd3 is
+//    only ever written) and which changed the HEAD = true code.
+#define BT_KERNEL_PARAMS                                                  \
+    const float* __restrict__ w2, const float* __restrict__ wf1,          \
+    const float* __restrict__ wf2,                                        \
+    const int64_t* __restrict__ tgt,                                      \
+    const float* __restrict__ gl,      /* dLoss (device scalar) */        \
+    const uint8_t* __restrict__ idx1_ws,                                  \
+    const uint8_t* __restrict__ m2_ws,                                    \
+    const uint8_t* __restrict__ idx2_ws,                                  \
+    const float* __restrict__ h1_ws,                                      \
+    const uint8_t* __restrict__ m3_ws,                                    \
+    const float* __restrict__ logp_ws,                                    \
+    float* __restrict__ glog_ws, float* __restrict__ gh1_ws,              \
+    float* __restrict__ ga2_ws, float* __restrict__ ga1_ws,               \
+    int B, int training, int split
+#define BT_KERNEL_ARGS                                                    \
+    w2, wf1, wf2, tgt, gl, idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws, logp_ws, \
+    glog_ws, gh1_ws, ga2_ws, ga1_ws, B, training, split
+
+template <bool HEAD>
+__device__ __forceinline__ void net_bwd_tiled_body(
+    BT_KERNEL_PARAMS,
+    // LDS carve (sizes: 5600, 6640, 3600; with the head 10, 50, 50, 320)
+    float* w2p, float* gd2p, float* part, float* glg, float* gd3,
+    float* gh1, float* gp2) {
   const int tid = threadIdx.x;
 
   // the grid is B * split or a multiple of 8 (host), so a workgroup
@@ -1252,25 +1439,56 @@ net_fused_bwd_tiled_kernel(
   const int ppr = BT_ROUND / nc;  // positions per round
 
   STAGE_STAMP(0);
+  // !HEAD: lane t < 320 moves float4 t of ga2_ws[b], the half-row
+  // (k, oh, 4*hc .. 4*hc+3), to tile entry (k, oh + 4, 4*hc + 4)
+  const int t_k = tid >> 4, t_oh = (tid >> 1) & 7, t_hc = tid & 1;
+  float4* const t_dst = reinterpret_cast<float4*>(
+      gd2p + t_k * BT_PS + (t_oh + 4) * BT_RS + 4 + 4 * t_hc);
+  float4 t_v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!HEAD && tid < N_A2 / 4 && (int)blockIdx.x < B * split)
+    t_v = reinterpret_cast<const float4*>(
+        ga2_ws + (int64_t)(blockIdx.x / split) * N_A2)[tid];
   for (int i = tid; i < N_C2K * nc * 25; i += BT_NT) {
     const int kc = i / 25, j = i - kc * 25;
     const int k = kc / nc, cl = kc - k * nc;
     w2p[kc * BT_WS + j] = w2[(k * N_C1K + c0 + cl) * 25 + j];
   }
-  const float sc = gl[0] / B;
+  float sc = 0.f;
+  if (HEAD) sc = gl[0] / B;
+  if (!HEAD) {
+    // the tile's ring: everything outside rows and columns 4..11 of a
+    // plane (and the plane's 12 pad floats); no sample writes it
+    for (int i = tid; i < N_C2K * BT_PS; i += BT_NT) {
+      const int r = i % BT_PS, row = r / BT_RS, col = r - row * BT_RS;
+      if (row < 4 || row > 11 || col < 4 || col > 11) gd2p[i] = 0.f;
+    }
+  }
 
   for (int bb = blockIdx.x; bb < B * split; bb += gridDim.x) {
     const int b = bb / split;
-    // (its leading barrier also orders the w2p staging and the previous
-    // sample's last tile reads)
-    // opaque per sample: with one g_p2 output per lane the 50 wf1
-    // loads are loop-invariant, and hoisted out of this loop they
-    // spilled 105 registers to scratch
-    const float* wf1_b = wf1;
-    asm volatile("" : "+s"(wf1_b));
-    net_bwd_head<BT_NT, BT_RS, BT_PS>(
-        b, half, tid, training, sc, wf1_b, wf2, tgt, m2_ws, idx2_ws, h1_ws,
-        m3_ws, logp_ws, glog_ws, gh1_ws, ga2_ws, glg, gd3, gh1, gp2, gd2p);
+    if (HEAD) {
+      // (its leading barrier also orders the w2p staging and the previous
+      // sample's last tile reads)
+      // opaque per sample: with one g_p2 output per lane the 50 wf1
+      // loads are loop-invariant, and hoisted out of this loop they
+      // spilled 105 registers to scratch
+      const float* wf1_b = wf1;
+      asm volatile("" : "+s"(wf1_b));
+      net_bwd_head<BT_NT, BT_RS, BT_PS>(
+          b, half, tid, training, sc, wf1_b, wf2, tgt, m2_ws, idx2_ws, h1_ws,
+          m3_ws, logp_ws, glog_ws, gh1_ws, ga2_ws, glg, gd3, gh1, gp2, gd2p);
+    } else {
+      if (bb != (int)blockIdx.x && tid < N_A2 / 4)
+        t_v = reinterpret_cast<const float4*>(
+            ga2_ws + (int64_t)b * N_A2)[tid];
+      // (the previous sample's tile reads ended on a barrier; the first
+      // sample's store may run beside the staging, which writes w2p and
+      // the ring only)
+      STAGE_STAMP(1);
+      if (tid < N_A2 / 4) *t_dst = t_v;
+      __syncthreads();
+      STAGE_STAMP(19);
+    }
 
     for (int pb = p0; pb < p1; pb += ppr) {
       const int nt = min(ppr, p1 - pb) * nc;  // tiles this round
@@ -1374,6 +1592,30 @@ net_fused_bwd_tiled_kernel(
     }
     STAGE_STAMP(8);
   }
+}
+
+__global__ void
+__launch_bounds__(BT_NT)
+net_fused_bwd_tiled_kernel(BT_KERNEL_PARAMS) {
+  __shared__ __attribute__((aligned(16))) float w2p[N_C2K * N_C1K * BT_WS];
+  __shared__ __attribute__((aligned(16))) float gd2p[N_C2K * BT_PS];
+  __shared__ __attribute__((aligned(16))) float part[BT_ROUND * BT_KG * 8];
+  __shared__ float glg[N_CLS];
+  __shared__ float gd3[N_H1];
+  __shared__ float gh1[N_H1];
+  __shared__ float gp2[N_P2];
+  net_bwd_tiled_body<true>(BT_KERNEL_ARGS, w2p, gd2p, part, glg, gd3, gh1,
+                           gp2);
+}
+
+__global__ void
+__launch_bounds__(BT_NT)
+net_fused_bwd_tiled_nohead_kernel(BT_KERNEL_PARAMS) {
+  __shared__ __attribute__((aligned(16))) float w2p[N_C2K * N_C1K * BT_WS];
+  __shared__ __attribute__((aligned(16))) float gd2p[N_C2K * BT_PS];
+  __shared__ __attribute__((aligned(16))) float part[BT_ROUND * BT_KG * 8];
+  net_bwd_tiled_body<false>(BT_KERNEL_ARGS, w2p, gd2p, part, nullptr,
+                            nullptr, nullptr, nullptr);
 }
 
 // Combined forward + data-backward in ONE kernel (round-2 experiment,
@@ -2319,14 +2561,19 @@ constexpr int FWD_POLL_BOUND = 60000;
 // sample (grid 2B, blockIdx = 2b + half) or one (grid_for(B, 1)).  The
 // four kernels share their leading parameters; poll_bound reaches the
 // tiled split kernel only (the old one polls 60000 times).
+// gl (the tiled kernels only): the device loss gradient, which turns on
+// the head of the data backward in the forward; 0 = off.
 static void launch_fwd(uintptr_t x, const GwPtrs& prm, uintptr_t tgt,
                        const NetWs& w, float* loss_part, uintptr_t seed_dev,
                        int B, bool training, bool tiled, int split,
-                       int poll_bound, hipStream_t s) {
+                       int poll_bound, uintptr_t gl, hipStream_t s) {
   if (tiled && (x & 15))
     throw std::invalid_argument(
         "net_fused_fwd: x must be 16-byte aligned (DTP_FWD_TILED=0 has "
         "no such requirement)");
+  if (gl && !tiled)
+    throw std::invalid_argument(
+        "net_fused_fwd: only the tiled forward runs the backward's head");
   auto launch = [&](auto kern, int grid, int block, auto... extra) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, s,
                        (const float*)x, prm.p[G_W1], prm.p[G_B1],
@@ -2339,39 +2586,58 @@ static void launch_fwd(uintptr_t x, const GwPtrs& prm, uintptr_t tgt,
   };
   if (split == 2 && tiled)
     launch(net_fused_fwd_tiled_kernel<true>, 2 * B, FT_NT, fwd_flags_buf(s),
-           fwd_token(), poll_bound);
+           fwd_token(), poll_bound, (const float*)gl, w.glog, w.gh1, w.ga2);
   else if (split == 2)
     launch(net_fused_fwd_split_kernel, 2 * B, 256, fwd_flags_buf(s),
            fwd_token());
   else if (tiled)
     launch(net_fused_fwd_tiled_kernel<false>, grid_for(B, 1), FT_NT,
-           (unsigned int*)nullptr, 0u, 0);
+           (unsigned int*)nullptr, 0u, 0, (const float*)gl, w.glog, w.gh1,
+           w.ga2);
   else
     launch(net_fused_fwd_kernel, grid_for(B, 1), 256);
 }
 
-void net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
+static bool bwd_tiled();
+
+// Whether the forward runs the head of the data backward (g_logits, g_h1,
+// g_p2 -> ga2), so that the backward starts from ga2.  It needs the loss
+// gradient before the forward (the step paths pass it; the autograd path
+// cannot) and both tiled kernels.  DTP_HEAD_IN_FWD=0 turns it off; read
+// on every call, like its neighbours.
+static bool head_in_fwd(uintptr_t gl, int B) {
+  if (!gl || !fwd_tiled(B) || !bwd_tiled()) return false;
+  const char* e = std::getenv("DTP_HEAD_IN_FWD");
+  return !(e && std::atoi(e) == 0);
+}
+
+// Returns whether the head of the data backward ran (gl given, see
+// head_in_fwd); the caller hands that on to net_fused_bwd as head_done.
+bool net_fused_fwd(uintptr_t x, const std::vector<uintptr_t>& prm_v,
                    uintptr_t tgt, const std::vector<uintptr_t>& ws_v,
                    bool use_loss_part, uintptr_t seed_dev, int B,
-                   bool training, uintptr_t stream) {
+                   bool training, uintptr_t stream, uintptr_t gl) {
   const NetWs w = net_ws(ws_v);
   const GwPtrs prm = gw_ptrs(prm_v, "net_fused_fwd params");
+  const bool head = head_in_fwd(gl, B);
   if (!use_loss_part)
     hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0,
                        S(stream), (unsigned long long*)nullptr, w.loss);
   launch_fwd(x, prm, tgt, w, use_loss_part ? w.loss_part : nullptr,
              seed_dev, B, training, fwd_tiled(B), fwd_split(B),
-             FWD_POLL_BOUND, S(stream));
+             FWD_POLL_BOUND, head ? gl : 0, S(stream));
+  return head;
 }
 
 // raw forward launch in loss_part mode with the kernel, the sibling split
 // and the poll bound given (microbenchmarks; tests force the hand-off's
 // fallback with poll_bound 0).  The loss partials are those of a
-// split-`split` grid, whatever fwd_grid(B) says.
+// split-`split` grid, whatever fwd_grid(B) says.  A non-zero gl (tiled
+// only) runs the head of the data backward as well.
 void net_fwd_raw(uintptr_t x, const std::vector<uintptr_t>& prm_v,
                  uintptr_t tgt, const std::vector<uintptr_t>& ws_v,
                  uintptr_t seed_dev, int B, bool training, bool tiled,
-                 int split, int poll_bound, uintptr_t stream) {
+                 int split, int poll_bound, uintptr_t stream, uintptr_t gl) {
   if (B < 1) throw std::invalid_argument("net_fwd_raw: B must be >= 1");
   if (split != 1 && split != 2)
     throw std::invalid_argument("net_fwd_raw: split must be 1 or 2");
@@ -2381,7 +2647,7 @@ void net_fwd_raw(uintptr_t x, const std::vector<uintptr_t>& prm_v,
     throw std::invalid_argument("net_fwd_raw: poll_bound must be >= 0");
   const NetWs w = net_ws(ws_v);
   launch_fwd(x, gw_ptrs(prm_v, "net_fwd_raw params"), tgt, w, w.loss_part,
-             seed_dev, B, training, tiled, split, poll_bound, S(stream));
+             seed_dev, B, training, tiled, split, poll_bound, gl, S(stream));
 }
 
 // sibling workgroups per sample of the data backward: enough to fill
@@ -2409,12 +2675,20 @@ static bool bwd_tiled() {
   return !(e && std::atoi(e) == 0);
 }
 
+// head_done: the forward of this step ran the head (net_fused_fwd said
+// so), glog / gh1 / ga2 are in the workspace and the tiled kernel starts
+// from ga2.
 static void launch_bwd_data(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
                             uintptr_t tgt, uintptr_t gl, const NetWs& w,
-                            int B, bool training, hipStream_t s) {
+                            int B, bool training, bool head_done,
+                            hipStream_t s) {
   const int split = bwd_split(B);
-  auto* kern = bwd_tiled() ? net_fused_bwd_tiled_kernel
-                           : net_fused_bwd_kernel;
+  if (head_done && !bwd_tiled())
+    throw std::invalid_argument(
+        "net_fused_bwd: head_done needs the tiled data backward");
+  auto* kern = !bwd_tiled() ? net_fused_bwd_kernel
+               : head_done  ? net_fused_bwd_tiled_nohead_kernel
+                            : net_fused_bwd_tiled_kernel;
   hipLaunchKernelGGL(kern, dim3(grid_for((int64_t)B * split, 1)),
                      dim3(bwd_tiled() ? BT_NT : 256), 0, s,
                      (const float*)w2, (const float*)wf1, (const float*)wf2,
@@ -2452,7 +2726,8 @@ static void launch_gw(const float* x, const NetWs& w, int B, GwPtrs gp,
 // Data backward + weight gradients.  A non-empty prm_v fuses the
 // SGD+momentum update into the combine (single-GPU path: no all-reduce
 // between combine and step).  Legacy mode (use_loss_part false) leaves
-// the loss scalar to the forward's atomics.
+// the loss scalar to the forward's atomics.  head_done: what this step's
+// net_fused_fwd returned.
 void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
                    uintptr_t tgt, uintptr_t gl,
                    const std::vector<uintptr_t>& ws_v,
@@ -2460,12 +2735,13 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
                    const std::vector<uintptr_t>& prm_v,
                    const std::vector<uintptr_t>& buf_v, double lr, double mu,
                    int B, bool training, bool use_loss_part,
-                   uintptr_t seed_dev, uintptr_t stream) {
+                   uintptr_t seed_dev, uintptr_t stream, bool head_done) {
   const NetWs w = net_ws(ws_v);
   const GwPtrs gp = gw_ptrs(grd_v, "net_fused_bwd grads");
   const bool sgd = !prm_v.empty();
   const GwPtrs pp = sgd ? gw_ptrs(prm_v, "net_fused_bwd params") : GwPtrs{};
-  launch_bwd_data(w2, wf1, wf2, tgt, gl, w, B, training, S(stream));
+  launch_bwd_data(w2, wf1, wf2, tgt, gl, w, B, training, head_done,
+                  S(stream));
   launch_gw((const float*)x, w, B, gp, pp, buf_ptrs(buf_v), (float)lr,
             (float)mu, sgd, use_loss_part ? w.loss_part : nullptr,
             use_loss_part ? w.loss : nullptr, fwd_grid(B),
@@ -2477,10 +2753,10 @@ void net_fused_bwd(uintptr_t x, uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
 void net_bwd_data_raw(uintptr_t w2, uintptr_t wf1, uintptr_t wf2,
                       uintptr_t tgt, uintptr_t gl,
                       const std::vector<uintptr_t>& ws_v, int B,
-                      bool training, uintptr_t stream) {
+                      bool training, uintptr_t stream, bool head_done) {
   if (B < 1) throw std::invalid_argument("net_bwd_data_raw: B must be >= 1");
   launch_bwd_data(w2, wf1, wf2, tgt, gl, net_ws(ws_v), B, training,
-                  S(stream));
+                  head_done, S(stream));
 }
 
 #ifdef DTP_STAGE_STAMPS
@@ -2681,10 +2957,24 @@ void net_step(uintptr_t x, uintptr_t tgt, uintptr_t gl,
 }  // namespace
 
 void register_net_fused(pybind11::module_& m) {
-  m.def("net_fused_fwd", &net_fused_fwd);
-  m.def("net_fwd_raw", &net_fwd_raw);
-  m.def("net_fused_bwd", &net_fused_bwd);
-  m.def("net_bwd_data_raw", &net_bwd_data_raw);
+  // (named only so that the trailing gl / head_done can default: calls
+  // written before the head moved into the forward stay valid)
+  using py::arg;
+  m.def("net_fused_fwd", &net_fused_fwd, arg("x"), arg("params"),
+        arg("tgt"), arg("ws"), arg("use_loss_part"), arg("seed_dev"),
+        arg("B"), arg("training"), arg("stream"), arg("gl") = (uintptr_t)0);
+  m.def("net_fwd_raw", &net_fwd_raw, arg("x"), arg("params"), arg("tgt"),
+        arg("ws"), arg("seed_dev"), arg("B"), arg("training"), arg("tiled"),
+        arg("split"), arg("poll_bound"), arg("stream"),
+        arg("gl") = (uintptr_t)0);
+  m.def("net_fused_bwd", &net_fused_bwd, arg("x"), arg("w2"), arg("wf1"),
+        arg("wf2"), arg("tgt"), arg("gl"), arg("ws"), arg("grads"),
+        arg("params"), arg("bufs"), arg("lr"), arg("mu"), arg("B"),
+        arg("training"), arg("use_loss_part"), arg("seed_dev"),
+        arg("stream"), arg("head_done") = false);
+  m.def("net_bwd_data_raw", &net_bwd_data_raw, arg("w2"), arg("wf1"),
+        arg("wf2"), arg("tgt"), arg("gl"), arg("ws"), arg("B"),
+        arg("training"), arg("stream"), arg("head_done") = false);
 #ifdef DTP_STAGE_STAMPS
   m.def("stage_stamps", &stage_stamps);
   m.def("stage_stamps_clear", &stage_stamps_clear);

@@ -9,7 +9,13 @@ sibling workgroups per sample at small batches, per-block loss partials;
 DTP_FWD_TILED=0 selects the earlier 256-thread kernels), one for the
 data backward (sibling-workgroup split,
 2x4-tile register-blocked transposed conv with the conv2 channels split
-over lanes), one segmented partial
+over lanes).  In the step paths (net_fused_step / _opt, whose loss
+gradient is the constant 1) the tiled forward also runs the HEAD of the
+data backward, loss gradient -> g_logits -> g_h1 -> g_p2 -> the dense
+conv2-output gradient ga2, on the values it still holds in LDS, and the
+tiled backward starts from ga2 (DTP_HEAD_IN_FWD=0 keeps the head in the
+backward; the autograd path net_fused_loss, whose upstream gradient
+arrives after the forward, always does).  Then one segmented partial
 weight-gradient kernel ([conv2 x8 | conv1 x8 | fc1 | fc2] tiles x batch
 chunks), and one combine kernel that also finalizes the loss, advances
 the dropout seed, and (single-GPU) applies the SGD+momentum update.
@@ -180,12 +186,17 @@ def _fwd_bwd(net, x, tgt, opt) -> torch.Tensor:
     params = _params(net)
     prm = _ptrs(params)
     s = _stream()
-    k.net_fused_fwd(x.data_ptr(), prm, tgt.data_ptr(), ws.ptrs, True,
-                    _seed_ptr(x.device), B, net.training, s)
+    # the loss gradient is the constant 1 and known up front, so the
+    # forward may run the head of the data backward (it says whether it
+    # did; the backward then starts from ga2)
+    one = ws["one"].data_ptr()
+    head_done = k.net_fused_fwd(x.data_ptr(), prm, tgt.data_ptr(), ws.ptrs,
+                                True, _seed_ptr(x.device), B, net.training,
+                                s, one)
     k.net_fused_bwd(x.data_ptr(), prm[2], prm[4], prm[6], tgt.data_ptr(),
-                    ws["one"].data_ptr(), ws.ptrs,
+                    one, ws.ptrs,
                     _ptrs(p.grad for p in params), *_sgd(opt, params), B,
-                    net.training, True, _seed_ptr(x.device), s)
+                    net.training, True, _seed_ptr(x.device), s, head_done)
     return ws["loss"]
 
 
