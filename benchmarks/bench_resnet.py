@@ -55,6 +55,11 @@ def main():
                    help="with --compute-dtype bf16: channels_last builds "
                         "the model with memory_format=torch.channels_last, "
                         "its own HIP ops on [B][H][W][C] storage")
+    p.add_argument("--fused-bn-stats", action="store_true",
+                   help="with --memory-format channels_last: every conv "
+                        "that feeds a batch norm computes the batch "
+                        "statistics' partials in its epilogue "
+                        "(resnet50(fused_bn_stats=True))")
     p.add_argument("--own-step", action="store_true",
                    help="with --compute-dtype bf16: the loss is "
                         "ops.cross_entropy and the optimizer FusedSGD "
@@ -67,6 +72,8 @@ def main():
     own_nhwc = args.memory_format == "channels_last"
     if own_nhwc and not own_bf16:
         p.error("--memory-format channels_last needs --compute-dtype bf16")
+    if args.fused_bn_stats and not own_nhwc:
+        p.error("--fused-bn-stats needs --memory-format channels_last")
     if own_bf16:
         args.channels_last = False
         args.dtype = "fp32"      # no autocast: the model casts itself
@@ -90,7 +97,8 @@ def main():
     torch.manual_seed(1234)
     if own_nhwc:
         model = resnet50(compute_dtype=torch.bfloat16,
-                         memory_format=torch.channels_last).to(device)
+                         memory_format=torch.channels_last,
+                         fused_bn_stats=args.fused_bn_stats).to(device)
     else:
         model = (resnet50(compute_dtype=torch.bfloat16) if own_bf16
                  else resnet50()).to(device)
@@ -188,6 +196,7 @@ def main():
                        "parallelism": f"dp{world}",
                        "channels_last": args.channels_last,
                        "memory_format": args.memory_format,
+                       "fused_bn_stats": args.fused_bn_stats,
                        "miopen_find": not args.no_find,
                        "grad_sync": "average_gradients"
                        if args.no_overlap else

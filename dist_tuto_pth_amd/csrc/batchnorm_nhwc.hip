@@ -20,6 +20,11 @@
 //                              channels to (count, mean, M2) in ws[C][S][3]:
 //                              the slice mean first, then the centred second
 //                              moment in a second, L2-resident pass
+//   bn_nhwc_merge_kernel       the statistics from the partials (mean, M2)
+//                              per 64-row tile that the convolution which
+//                              produced x wrote in its epilogue
+//                              (conv_nhwc_bf16.hip), instead of the stats
+//                              and finalize kernels: see below
 //   bn_nhwc_apply_kernel       y = relu?((x-mean)*(gamma*invstd)+beta (+res))
 //   bn_nhwc_bwd_reduce_kernel  grid (column tiles, S): partial dbeta /
 //                              dgamma, ws[C][S][2]
@@ -33,6 +38,20 @@
 // depends on C alone, so every sum is fixed by (rows, C, S) and not by V,
 // the alignment or the dtype: the bf16 result is the fp32 one on the same
 // values rounded once, and a misaligned view gives the bits of its clone.
+//
+// Merge order of bn_nhwc_merge_kernel.  T = ceil(rows/64) partials per
+// channel, partial t covering rows [64t, min(rows, 64t+64)), are merged
+// with Chan's formula on levels of 256: at a level with P partials of
+// `span` rows each, group g = partials [256g, min(P, 256g+256)); in it
+// tile lane l (of 16) merges partials 256g + l, + 16, + 32, ... in
+// ascending order, at most 16 of them, then the 16 lanes are merged in
+// lane order through LDS.  The groups' results are the next level's
+// partials, span*256 rows each, until one group is left.  A thread's serial
+// chain is at most 16 + 15 merges per level whatever T is; the number of
+// levels is ceil(log256 T): 1 up to 16,384 rows, 2 up to 4,194,304.  Counts
+// are never stored, every level derives them from (rows, span).  The order
+// depends on (rows, C) only (C: which block holds a channel, not the
+// order).  Adjacent threads read adjacent channels: 16 x 8 bytes per lane.
 //
 // The apply kernels load mean, gamma*invstd, beta (and dbeta/n, dgamma/n)
 // of their V channels once into registers and then stride over rows; the
@@ -106,6 +125,92 @@ __global__ __launch_bounds__(BLK) void bn_nhwc_stats_kernel(
     o[0] = cnt;
     o[1] = mean;
     o[2] = m2;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// forward statistics from the convolution's partials
+// ---------------------------------------------------------------------------
+// Chan's merge of (na, mean, m2) with (nb, mb, m2b), nb > 0: the arithmetic
+// of bn_finalize_kernel
+__device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2,
+                                           float nb, float mb, float m2b) {
+  const float nab = n + nb, delta = mb - mean;
+  mean += delta * (nb / nab);
+  m2 += m2b + delta * delta * (n * (nb / nab));
+  n = nab;
+}
+
+constexpr int MG_CL = 16;     // channels of a block, adjacent threads
+constexpr int MG_L = BLK / MG_CL;  // tile lanes
+constexpr int MG_CHAIN = 16;  // partials a lane merges, at most
+constexpr int MG_GROUP = MG_L * MG_CHAIN;  // partials a block merges
+
+// in[P][C][2] holds (mean, M2) of the rows [p*span, min(rows, (p+1)*span))
+// of every channel; P = ceil(rows / span).  grid = (ceil(C / MG_CL), groups),
+// groups = ceil(P / MG_GROUP).  Block (t, g) merges the partials
+// [g*MG_GROUP, min(P, (g+1)*MG_GROUP)) of its 16 channels: thread (lane l,
+// channel c) the partials g*MG_GROUP + l, + MG_L, ... in ascending order,
+// then thread (0, c) the 16 lanes in lane order through LDS.  With one
+// group the result is final: save_mean, save_invstd and the running update
+// of bn_finalize_kernel.  With more, it is partial g of out[groups][C][2],
+// whose span is span*MG_GROUP, and the host launches the kernel again on
+// those.  No count is ever stored: every level derives it from (rows, span).
+template <bool FINAL>
+__global__ __launch_bounds__(BLK) void bn_nhwc_merge_kernel(
+    const float* __restrict__ in, uint32_t P, uint32_t span, uint32_t rows,
+    uint32_t C, float* __restrict__ out, float eps, float momentum,
+    float* __restrict__ save_mean, float* __restrict__ save_invstd,
+    float* __restrict__ run_mean, float* __restrict__ run_var) {
+  __shared__ float sh[3][MG_L][MG_CL];
+  const uint32_t cl = threadIdx.x % MG_CL, l = threadIdx.x / MG_CL;
+  const uint32_t c = blockIdx.x * MG_CL + cl;
+  const uint32_t p0 = blockIdx.y * MG_GROUP;
+  const uint32_t pend = min(P, p0 + MG_GROUP);
+
+  float n = 0.f, mean = 0.f, m2 = 0.f;
+  if (c < C) {
+    // the loads do not depend on the merges: all in flight together
+    float2 v[MG_CHAIN];
+#pragma unroll
+    for (int j = 0; j < MG_CHAIN; ++j) {
+      const uint32_t p = p0 + l + j * MG_L;
+      v[j] = *reinterpret_cast<const float2*>(
+          in + ((int64_t)(p < pend ? p : p0) * C + c) * 2);
+    }
+#pragma unroll
+    for (int j = 0; j < MG_CHAIN; ++j) {
+      const uint32_t p = p0 + l + j * MG_L;
+      if (p < pend) {
+        const float nb = (float)min(span, rows - p * span);
+        if (j == 0) {
+          n = nb; mean = v[0].x; m2 = v[0].y;
+        } else {
+          chan_merge(n, mean, m2, nb, v[j].x, v[j].y);
+        }
+      }
+    }
+  }
+  sh[0][l][cl] = n;
+  sh[1][l][cl] = mean;
+  sh[2][l][cl] = m2;
+  __syncthreads();
+  if (l != 0 || c >= C) return;
+  // lane 0 always has a partial; lanes are filled in ascending order
+  for (int i = 1; i < MG_L && sh[0][i][cl] > 0.f; ++i)
+    chan_merge(n, mean, m2, sh[0][i][cl], sh[1][i][cl], sh[2][i][cl]);
+  if (!FINAL) {
+    *reinterpret_cast<float2*>(out + ((int64_t)blockIdx.y * C + c) * 2) =
+        make_float2(mean, m2);
+    return;
+  }
+  const float var = m2 / n;
+  save_mean[c] = mean;
+  save_invstd[c] = 1.f / sqrtf(var + eps);
+  if (run_mean) {
+    const float keep = 1.f - momentum;
+    run_mean[c] = keep * run_mean[c] + momentum * mean;
+    run_var[c] = keep * run_var[c] + momentum * (var * (n / (n - 1.f)));
   }
 }
 
@@ -301,6 +406,24 @@ int64_t apply_rows_grid(int64_t rows, int64_t C, int v, int sh) {
   return std::min(want, std::max<int64_t>(1, 4096 / tiles));
 }
 
+// y from x and the per-channel (mean, stat): the last launch of a forward
+void launch_apply(uintptr_t x, uintptr_t res, uintptr_t y, uintptr_t gamma,
+                  uintptr_t beta, uintptr_t mean, uintptr_t stat,
+                  int64_t rows, int64_t C, bool training, double eps,
+                  bool relu, bool is_bf16, uintptr_t stream) {
+  const int es = is_bf16 ? 2 : 4, sh = nhwc_cl_shift(C);
+  by_dtype_width(is_bf16, pick_v(es, C, {x, res, y}), [&](auto* t, auto v) {
+    using T = elem_t<decltype(t)>;
+    hipLaunchKernelGGL(
+        (bn_nhwc_apply_kernel<T, v()>),
+        tile_grid(C, v(), sh, apply_rows_grid(rows, C, v(), sh)), dim3(BLK),
+        0, S(stream), (const T*)x, (const T*)res, (T*)y, (const float*)mean,
+        (const float*)stat, (const float*)gamma, (const float*)beta,
+        (float)eps, (int)!training, (int)relu, (uint32_t)rows, (uint32_t)C,
+        sh);
+  });
+}
+
 // batchnorm2d_fwd's contract on [rows][C] storage, rows = B*H*W
 void batchnorm2d_nhwc_fwd(uintptr_t x, uintptr_t res, uintptr_t y,
                           uintptr_t gamma, uintptr_t beta, uintptr_t run_mean,
@@ -340,18 +463,75 @@ void batchnorm2d_nhwc_fwd(uintptr_t x, uintptr_t res, uintptr_t y,
                        (float*)save_invstd, (float*)run_mean,
                        (float*)run_var);
   }
-  const uintptr_t mean = training ? save_mean : run_mean;
-  const uintptr_t stat = training ? save_invstd : run_var;
-  by_dtype_width(is_bf16, pick_v(es, C, {x, res, y}), [&](auto* t, auto v) {
-    using T = elem_t<decltype(t)>;
-    hipLaunchKernelGGL(
-        (bn_nhwc_apply_kernel<T, v()>),
-        tile_grid(C, v(), sh, apply_rows_grid(rows, C, v(), sh)), dim3(BLK),
-        0, S(stream), (const T*)x, (const T*)res, (T*)y, (const float*)mean,
-        (const float*)stat, (const float*)gamma, (const float*)beta,
-        (float)eps, (int)!training, (int)relu, (uint32_t)rows, (uint32_t)C,
-        sh);
-  });
+  launch_apply(x, res, y, gamma, beta, training ? save_mean : run_mean,
+               training ? save_invstd : run_var, rows, C, training, eps, relu,
+               is_bf16, stream);
+  HIP_CHECK(hipGetLastError());
+}
+
+// How many floats of workspace batchnorm2d_nhwc_fwd_from_partials needs
+// for the levels above the convolution's partials: 0 up to MG_GROUP tiles.
+int64_t batchnorm2d_nhwc_merge_ws(int64_t rows, int64_t C) {
+  check_dims(rows, C, 1);
+  int64_t P = (rows + BN_PARTIAL_ROWS - 1) / BN_PARTIAL_ROWS, n = 0;
+  while (P > MG_GROUP) {
+    P = (P + MG_GROUP - 1) / MG_GROUP;
+    n += P * C * 2;
+  }
+  return n;
+}
+
+// batchnorm2d_nhwc_fwd in training, starting from the partial statistics
+// tws[tiles][C][2] = (mean, M2) of x's rows [t*64, min(rows, (t+1)*64)) that
+// the convolution which produced x wrote (conv2d_nhwc_bf16_fwd_stats)
+// instead of from a pass over x: one merge launch per level (one up to 256
+// tiles, two up to 65536, three beyond), then the apply kernel.  ws holds
+// batchnorm2d_nhwc_merge_ws(rows, C) floats, 0 where that is 0.
+void batchnorm2d_nhwc_fwd_from_partials(
+    uintptr_t x, uintptr_t res, uintptr_t y, uintptr_t gamma, uintptr_t beta,
+    uintptr_t run_mean, uintptr_t run_var, uintptr_t save_mean,
+    uintptr_t save_invstd, uintptr_t tws, uintptr_t ws, int64_t rows,
+    int64_t C, double momentum, double eps, bool relu, bool is_bf16,
+    uintptr_t stream) {
+  check_dims(rows, C, 1);
+  if (!x || !y || !gamma || !beta || !save_mean || !save_invstd || !tws)
+    throw std::invalid_argument("batchnorm2d_nhwc: null tensor");
+  if (tws % 8 || ws % 8)
+    throw std::invalid_argument(
+        "batchnorm2d_nhwc: the partials must be 8-byte aligned");
+  if (rows < 2)
+    throw std::invalid_argument(
+        "batchnorm2d: training needs more than one value per channel");
+  if ((run_mean == 0) != (run_var == 0))
+    throw std::invalid_argument(
+        "batchnorm2d: running_mean and running_var come together");
+  if (!ws && batchnorm2d_nhwc_merge_ws(rows, C) > 0)
+    throw std::invalid_argument("batchnorm2d_nhwc: no merge workspace");
+  const float* in = (const float*)tws;
+  float* next = (float*)ws;
+  int64_t span = BN_PARTIAL_ROWS;
+  int64_t P = (rows + span - 1) / span;
+  const unsigned ctiles = (unsigned)((C + MG_CL - 1) / MG_CL);
+  while (P > MG_GROUP) {  // span * MG_GROUP < rows: fits 32 bits
+    const int64_t groups = (P + MG_GROUP - 1) / MG_GROUP;
+    hipLaunchKernelGGL(bn_nhwc_merge_kernel<false>,
+                       dim3(ctiles, (unsigned)groups), dim3(BLK), 0,
+                       S(stream), in, (uint32_t)P, (uint32_t)span,
+                       (uint32_t)rows, (uint32_t)C, next, 0.f, 0.f,
+                       (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr);
+    in = next;
+    next += groups * C * 2;
+    span *= MG_GROUP;
+    P = groups;
+  }
+  hipLaunchKernelGGL(bn_nhwc_merge_kernel<true>, dim3(ctiles, 1), dim3(BLK),
+                     0, S(stream), in, (uint32_t)P, (uint32_t)span,
+                     (uint32_t)rows, (uint32_t)C, (float*)nullptr, (float)eps,
+                     (float)momentum, (float*)save_mean, (float*)save_invstd,
+                     (float*)run_mean, (float*)run_var);
+  launch_apply(x, res, y, gamma, beta, save_mean, save_invstd, rows, C, true,
+               eps, relu, is_bf16, stream);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -400,5 +580,8 @@ void batchnorm2d_nhwc_bwd(uintptr_t x, uintptr_t gy, uintptr_t y,
 void register_batchnorm_nhwc(pybind11::module_& m) {
   m.def("batchnorm2d_nhwc_splits", &batchnorm2d_nhwc_splits);
   m.def("batchnorm2d_nhwc_fwd", &batchnorm2d_nhwc_fwd);
+  m.def("batchnorm2d_nhwc_merge_ws", &batchnorm2d_nhwc_merge_ws);
+  m.def("batchnorm2d_nhwc_fwd_from_partials",
+        &batchnorm2d_nhwc_fwd_from_partials);
   m.def("batchnorm2d_nhwc_bwd", &batchnorm2d_nhwc_bwd);
 }

@@ -27,6 +27,11 @@
 constexpr int BLK = 256;  // threads per block (4 waves): the elementwise
                           // kernels, the bf16 GEMM tile and batchnorm
 
+// Rows per partial (mean, M2) that the channels-last convolution's
+// statistics epilogue hands to batch norm: its GEMM row tile.  The partials
+// carry no count; both sides derive it from this.
+constexpr int BN_PARTIAL_ROWS = 64;
+
 static inline hipStream_t S(uintptr_t s) {
   return reinterpret_cast<hipStream_t>(s);
 }

@@ -32,6 +32,29 @@
 // thread writes 8 consecutive channels.  LDS per block is the two operand
 // tiles, 18432 bytes, as in linear_bf16.
 //
+// Forward with a statistics epilogue (conv_nhwc_stats_kernel, STATS = true;
+// ops.conv2d_bf16(..., bn_stats=True)).  Besides storing its tile, the block
+// reduces the live rows (m < M) of the staged OutT tile, i.e. the stored
+// values after their one rounding, bias included, to a per-channel mean and
+// centred second moment M2 = sum (v - mean)^2 in fp32, and writes them to
+// tws[row tile][N][2] with one 8-byte store per channel.  The count is not
+// stored: it is min(BM, M - m0).  Split of the 64x64 tile over the 256
+// threads: wave q owns rows [16q, 16q+16), lane c owns tile column c, so an
+// LDS read of a row is 64 adjacent elements and hits every bank once.  A
+// thread reads its 16 values once, keeps them in the registers the
+// accumulators have left, and adds the live ones in ascending row order;
+// the four waves' sums go through 4x64 floats of LDS and every thread adds
+// them in wave order 0..3 and divides by the count, so the four threads of
+// a channel hold the same mean.  The second pass runs over the same 16
+// values: d = v - mean, fmaf(d, d, .) in ascending row order, the four
+// partial M2 again added in wave order by thread c of wave 0.  Every sum's
+// order is fixed by (M, N) alone, whatever the load path (VEC) or the
+// alignment; there are no atomics.  The 1,024 bytes of scratch are the ones
+// the fp32 C tile leaves free in the operand tiles (the bf16 tile leaves
+// more), so LDS stays at 18,432 bytes.  The global stores of the tile are
+// issued before the reduction and fly under it.  STATS is a template flag:
+// the kernels without it are the ones they were.
+//
 // gw runs on gemm_bf16_block with both operands transposed on the LDS
 // write (the reduction runs along pixels, the chunks along channels).  Its
 // epilogue stores column (r,s,c) at the parameter's [K,C,R,S] position, so
@@ -261,10 +284,12 @@ constexpr int OPER_BYTES = (BM + BN) * LDS_LD * (int)sizeof(bf16_t);
 
 // out[m][n] = bias[n] + sum_kk A(m,kk) * w[n][kk], rounded once to OutT;
 // out is row-major [M][N].  grid = (m tiles, n tiles).
-template <bool GX, bool VEC, typename OutT>
-__global__ __launch_bounds__(BLK) void conv_nhwc_kernel(
+// STATS: also tws[blockIdx.x][n][0..1] = (mean, M2) of the block's live
+// rows of column n, from the staged (stored) values.
+template <bool GX, bool VEC, typename OutT, bool STATS>
+__device__ __forceinline__ void conv_nhwc_block(
     NhwcSrc a, Operand w, int M, int N, OutT* __restrict__ out,
-    const float* __restrict__ bias, int out_vec) {
+    const float* __restrict__ bias, int out_vec, float* __restrict__ tws) {
   // the C tile's pitch keeps rows 16-byte aligned and off a common bank
   constexpr int CT_PITCH = BN + 16 / (int)sizeof(OutT);
   static_assert(BM * CT_PITCH * sizeof(OutT) <= OPER_BYTES,
@@ -352,6 +377,63 @@ __global__ __launch_bounds__(BLK) void conv_nhwc_kernel(
         if (n + j < N) dst[j] = Ct[ml][nl + j];
     }
   }
+
+  if constexpr (STATS) {
+    static_assert(BN == 64 && BM % NWAVE == 0, "a lane per column");
+    constexpr int SEG = BM / NWAVE;  // rows per wave
+    constexpr int RED_OFF = OPER_BYTES - NWAVE * BN * (int)sizeof(float);
+    static_assert(BM * CT_PITCH * sizeof(OutT) <= RED_OFF,
+                  "the wave sums lie behind the C tile");
+    float (*red)[BN] = reinterpret_cast<float(*)[BN]>(smem + RED_OFF);
+    const int live = min(BM, M - m0);  // rows of this tile, >= 1
+    const int nrow = min(SEG, live - wave * SEG);  // of this wave, may be <= 0
+    float v[SEG];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) {
+      v[i] = to_f(Ct[wave * SEG + i][lane]);
+      if (i < nrow) s += v[i];
+    }
+    red[wave][lane] = s;
+    __syncthreads();
+    const float mean =
+        (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) /
+        (float)live;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < SEG; ++i)
+      if (i < nrow) {
+        const float d = v[i] - mean;
+        q = fmaf(d, d, q);
+      }
+    __syncthreads();  // every thread has read the sums
+    red[wave][lane] = q;
+    __syncthreads();
+    if (wave == 0 && n0 + lane < N) {
+      const float m2 =
+          ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+      *reinterpret_cast<float2*>(
+          tws + ((int64_t)blockIdx.x * N + n0 + lane) * 2) =
+          make_float2(mean, m2);
+    }
+  }
+}
+
+template <bool GX, bool VEC, typename OutT>
+__global__ __launch_bounds__(BLK) void conv_nhwc_kernel(
+    NhwcSrc a, Operand w, int M, int N, OutT* __restrict__ out,
+    const float* __restrict__ bias, int out_vec) {
+  conv_nhwc_block<GX, VEC, OutT, false>(a, w, M, N, out, bias, out_vec,
+                                        nullptr);
+}
+
+// the forward with the statistics epilogue
+template <bool VEC, typename OutT>
+__global__ __launch_bounds__(BLK) void conv_nhwc_stats_kernel(
+    NhwcSrc a, Operand w, int M, int N, OutT* __restrict__ out,
+    const float* __restrict__ bias, int out_vec, float* __restrict__ tws) {
+  conv_nhwc_block<false, VEC, OutT, true>(a, w, M, N, out, bias, out_vec,
+                                          tws);
 }
 
 // gw[k][(r,s,c)] = sum over pixels gy[pixel][k] * x[window(pixel)][r][s][c];
@@ -404,17 +486,31 @@ static bool chunks_are_vectors(const NhwcSrc& s) {
   return s.Cs % 8 == 0 && reinterpret_cast<uintptr_t>(s.p) % 16 == 0;
 }
 
-// out[M][N] from the gathered `a` and the packed weight wp[N][a.nred]
+// out[M][N] from the gathered `a` and the packed weight wp[N][a.nred];
+// with tws (forward only) through the statistics epilogue
 template <bool GX>
 static void launch_pixels(const NhwcSrc& a, uintptr_t wp, uintptr_t bias,
                           uintptr_t out, int M, int N, bool out_f32,
-                          uintptr_t stream) {
+                          uintptr_t stream, uintptr_t tws = 0) {
   const Operand b = operand(wp, a.nred, N);
   const dim3 grid(cdiv(M, BM), cdiv(N, BN), 1);
   const int out_vec = N % 8 == 0 && out % 16 == 0;
   const bool vec = chunks_are_vectors(a);
   by_dtype(!out_f32, [&](auto* t) {
     using OutT = elem_t<decltype(t)>;
+    if constexpr (!GX) {
+      if (tws) {
+        if (vec)
+          hipLaunchKernelGGL((conv_nhwc_stats_kernel<true, OutT>), grid,
+                             dim3(BLK), 0, S(stream), a, b, M, N, (OutT*)out,
+                             (const float*)bias, out_vec, (float*)tws);
+        else
+          hipLaunchKernelGGL((conv_nhwc_stats_kernel<false, OutT>), grid,
+                             dim3(BLK), 0, S(stream), a, b, M, N, (OutT*)out,
+                             (const float*)bias, out_vec, (float*)tws);
+        return;
+      }
+    }
     if (vec)
       hipLaunchKernelGGL((conv_nhwc_kernel<GX, true, OutT>), grid, dim3(BLK),
                          0, S(stream), a, b, M, N, (OutT*)out,
@@ -455,6 +551,30 @@ void conv2d_nhwc_bf16_fwd(uintptr_t x, uintptr_t wp, uintptr_t bias,
   const ConvDims d = conv_dims(B, C, H, W, K, R, S_, sh, sw, ph, pw);
   launch_pixels<false>(src_x(x, d), wp, bias, out, B * d.OH * d.OW, K,
                        out_f32, stream);
+}
+
+// The same, and tws[tiles][K][2] = (mean, M2) over the rows
+// [t*BM, min(B*OH*OW, (t+1)*BM)) of every output channel, taken from the
+// stored values; tiles = conv2d_nhwc_bf16_stats_tiles(B*OH*OW).  Every
+// element of tws is written.
+void conv2d_nhwc_bf16_fwd_stats(uintptr_t x, uintptr_t wp, uintptr_t bias,
+                                uintptr_t out, uintptr_t tws, int B, int C,
+                                int H, int W, int K, int R, int S_, int sh,
+                                int sw, int ph, int pw, bool out_f32,
+                                uintptr_t stream) {
+  if (!tws || tws % 8)
+    throw std::invalid_argument(
+        "conv2d_nhwc_bf16_fwd_stats: tws must be an 8-byte aligned buffer");
+  const ConvDims d = conv_dims(B, C, H, W, K, R, S_, sh, sw, ph, pw);
+  launch_pixels<false>(src_x(x, d), wp, bias, out, B * d.OH * d.OW, K,
+                       out_f32, stream, tws);
+}
+
+int64_t conv2d_nhwc_bf16_stats_tiles(int64_t rows) {
+  static_assert(BM == BN_PARTIAL_ROWS, "batch norm derives the counts");
+  if (rows < 1 || rows > MAX_DIM)
+    throw std::invalid_argument("conv2d_bf16: bad row count");
+  return (rows + BM - 1) / BM;
 }
 
 // gx[B,H,W,C] from gy[B,OH,OW,K] and wp[C][R][S][K]; every element is
@@ -518,6 +638,8 @@ void conv2d_nhwc_bf16_bwd_w(uintptr_t gy, uintptr_t x, uintptr_t gw,
 void register_conv_nhwc_bf16(pybind11::module_& m) {
   m.def("conv2d_nhwc_bf16_pack_w", &conv2d_nhwc_bf16_pack_w);
   m.def("conv2d_nhwc_bf16_fwd", &conv2d_nhwc_bf16_fwd);
+  m.def("conv2d_nhwc_bf16_fwd_stats", &conv2d_nhwc_bf16_fwd_stats);
+  m.def("conv2d_nhwc_bf16_stats_tiles", &conv2d_nhwc_bf16_stats_tiles);
   m.def("conv2d_nhwc_bf16_bwd_x", &conv2d_nhwc_bf16_bwd_x);
   m.def("conv2d_nhwc_bf16_gw_splits", &conv2d_nhwc_bf16_gw_splits);
   m.def("conv2d_nhwc_bf16_bwd_w", &conv2d_nhwc_bf16_bwd_w);

@@ -231,9 +231,10 @@ __global__ __launch_bounds__(BLK) void gap_nhwc_fwd_kernel(
   __shared__ float sh[BLK * V];
   const ColTile t = col_tile<V>(blockIdx.x, cl_shift, C);
   const uint32_t L = (uint32_t)BLK >> cl_shift;
-  const uint32_t c = (blockIdx.x << cl_shift) * V + threadIdx.x;
+  const uint32_t CT = (uint32_t)V << cl_shift;  // channels of a tile
+  const uint32_t c0 = blockIdx.x * CT;
   const float cnt = (float)HW;
-  // block-uniform loop: every thread reaches lane_combine's barriers
+  // block-uniform loop: every thread reaches the barriers
   for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
     const T* xp = x + b * HW * C + t.c;
     float acc[V];
@@ -248,9 +249,18 @@ __global__ __launch_bounds__(BLK) void gap_nhwc_fwd_kernel(
         for (int j = 0; j < V; ++j) acc[j] += f[j];
       }
     }
-    const float s = lane_combine<V>(acc, t, cl_shift, sh);
-    if (threadIdx.x < ((uint32_t)V << cl_shift) && c < C)
-      from_f(s / cnt, y[b * C + c]);
+    // lane_combine's sum, in its order, but for every channel of the tile:
+    // with fewer row lanes than V (H*W <= 16) the tile has more channels
+    // than the block has threads
+    __syncthreads();  // sh may still be read from the previous sample
+#pragma unroll
+    for (int j = 0; j < V; ++j) sh[t.rl * CT + t.cl * V + j] = acc[j];
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < CT && c0 + i < C; i += BLK) {
+      float s = sh[i];
+      for (uint32_t r = 1; r < L; ++r) s += sh[r * CT + i];
+      from_f(s / cnt, y[b * C + c0 + i]);
+    }
   }
 }
 

@@ -36,6 +36,14 @@ pool of the bf16 forward.  The stem conv lays the input batch out
 [B][H][W][C]; from there to the [B,C] pooled vector every activation and
 every gradient has channels-last storage, so no op copies a layout.
 Parameters, buffers and ``state_dict`` are the same in both layouts.
+
+``fused_bn_stats=True`` (only with ``memory_format=torch.channels_last``)
+makes every convolution that feeds a batch norm in training mode — the
+stem, the three of a block and the downsample — reduce its own output
+tiles to partial batch statistics (``ops.conv2d_bf16(..., bn_stats=True)``)
+and hands them to that batch norm (``batch_stats=``), which then skips its
+two statistics passes over the tensor.  Eval mode, parameters, buffers and
+``state_dict`` do not change.
 """
 
 from __future__ import annotations
@@ -68,6 +76,14 @@ def _check_memory_format(who, memory_format, compute_dtype):
     return memory_format
 
 
+def _check_fused_bn_stats(who, fused_bn_stats, memory_format):
+    if fused_bn_stats and memory_format != torch.channels_last:
+        raise ValueError(
+            f"{who}: fused_bn_stats=True needs "
+            f"memory_format=torch.channels_last")
+    return bool(fused_bn_stats)
+
+
 def _layout_kw(memory_format):
     """What the bf16 forward adds to every conv, BN and pool call: nothing
     in the default layout, whose calls stay exactly as they were."""
@@ -89,16 +105,36 @@ def _bn(bn, x, residual=None, fuse_relu=False, **layout):
                            residual=residual, fuse_relu=fuse_relu, **layout)
 
 
+def _conv_bn(conv, bn, x, fused, residual=None, fuse_relu=False, **layout):
+    """bn(conv(x)); with ``fused`` and a batch norm in training mode the
+    convolution computes the batch statistics' partials on the way."""
+    if not (fused and bn.training):
+        return _bn(bn, _conv_bf16(conv, x, **layout), residual, fuse_relu,
+                   **layout)
+    out, stats = ops.conv2d_bf16(x, conv.weight, None, stride=conv.stride,
+                                 padding=conv.padding,
+                                 out_dtype=torch.bfloat16, bn_stats=True,
+                                 **layout)
+    return ops.batchnorm2d(out, bn.weight, bn.bias, bn.running_mean,
+                           bn.running_var, training=True,
+                           momentum=bn.momentum, eps=bn.eps,
+                           residual=residual, fuse_relu=fuse_relu,
+                           batch_stats=stats, **layout)
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, in_ch, width, stride=1, downsample=None,
                  compute_dtype: Optional[torch.dtype] = None,
-                 memory_format=torch.contiguous_format):
+                 memory_format=torch.contiguous_format,
+                 fused_bn_stats=False):
         super().__init__()
         self.compute_dtype = _check_compute_dtype("Bottleneck", compute_dtype)
         self.memory_format = _check_memory_format(
             "Bottleneck", memory_format, compute_dtype)
+        self.fused_bn_stats = _check_fused_bn_stats(
+            "Bottleneck", fused_bn_stats, memory_format)
         out_ch = width * self.expansion
         self.conv1 = nn.Conv2d(in_ch, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
@@ -112,16 +148,15 @@ class Bottleneck(nn.Module):
 
     def _forward_bf16(self, x):
         mf = _layout_kw(self.memory_format)
-        out = _bn(self.bn1, _conv_bf16(self.conv1, x, **mf), fuse_relu=True,
-                  **mf)
-        out = _bn(self.bn2, _conv_bf16(self.conv2, out, **mf), fuse_relu=True,
-                  **mf)
+        fu = self.fused_bn_stats
+        out = _conv_bn(self.conv1, self.bn1, x, fu, fuse_relu=True, **mf)
+        out = _conv_bn(self.conv2, self.bn2, out, fu, fuse_relu=True, **mf)
         identity = x
         if self.downsample is not None:
-            identity = _bn(self.downsample[1],
-                           _conv_bf16(self.downsample[0], x, **mf), **mf)
-        return _bn(self.bn3, _conv_bf16(self.conv3, out, **mf),
-                   residual=identity, fuse_relu=True, **mf)
+            identity = _conv_bn(self.downsample[0], self.downsample[1], x, fu,
+                                **mf)
+        return _conv_bn(self.conv3, self.bn3, out, fu, residual=identity,
+                        fuse_relu=True, **mf)
 
     def forward(self, x):
         if self.compute_dtype is not None:
@@ -138,11 +173,14 @@ class Bottleneck(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes=1000,
                  compute_dtype: Optional[torch.dtype] = None,
-                 memory_format=torch.contiguous_format):
+                 memory_format=torch.contiguous_format,
+                 fused_bn_stats=False):
         super().__init__()
         self.compute_dtype = _check_compute_dtype("ResNet", compute_dtype)
         self.memory_format = _check_memory_format(
             "ResNet", memory_format, compute_dtype)
+        self.fused_bn_stats = _check_fused_bn_stats(
+            "ResNet", fused_bn_stats, memory_format)
         self.in_ch = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -172,19 +210,21 @@ class ResNet(nn.Module):
                 nn.BatchNorm2d(out_ch))
         layers = [Bottleneck(self.in_ch, width, stride, downsample,
                              compute_dtype=self.compute_dtype,
-                             memory_format=self.memory_format)]
+                             memory_format=self.memory_format,
+                             fused_bn_stats=self.fused_bn_stats)]
         self.in_ch = out_ch
         for _ in range(1, blocks):
             layers.append(Bottleneck(self.in_ch, width,
                                      compute_dtype=self.compute_dtype,
-                                     memory_format=self.memory_format))
+                                     memory_format=self.memory_format,
+                                     fused_bn_stats=self.fused_bn_stats))
         return nn.Sequential(*layers)
 
     def forward(self, x):
         if self.compute_dtype is not None:
             mf = _layout_kw(self.memory_format)
-            x = _bn(self.bn1, _conv_bf16(self.conv1, x, **mf), fuse_relu=True,
-                    **mf)
+            x = _conv_bn(self.conv1, self.bn1, x, self.fused_bn_stats,
+                         fuse_relu=True, **mf)
             x = ops.maxpool2d(x, self.maxpool.kernel_size,
                               self.maxpool.stride, self.maxpool.padding, **mf)
             x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
@@ -199,6 +239,7 @@ class ResNet(nn.Module):
 
 def resnet50(num_classes=1000,
              compute_dtype: Optional[torch.dtype] = None,
-             memory_format=torch.contiguous_format) -> ResNet:
+             memory_format=torch.contiguous_format,
+             fused_bn_stats=False) -> ResNet:
     return ResNet((3, 4, 6, 3), num_classes, compute_dtype=compute_dtype,
-                  memory_format=memory_format)
+                  memory_format=memory_format, fused_bn_stats=fused_bn_stats)

@@ -749,12 +749,34 @@ def _laid_out(t, nhwc):
     return _as_nhwc(t) if nhwc and t.is_cuda else t.contiguous()
 
 
+class ConvBatchStats:
+    """What ``conv2d_bf16(..., bn_stats=True)`` hands to
+    ``batchnorm2d(..., batch_stats=...)``: the per-channel partial
+    statistics of the convolution's output ``out`` and what identifies that
+    tensor.  Opaque: only those two functions read it.
+
+    ``partials`` is fp32 [tiles, K, 2] — the mean and the centred second
+    moment of ``out``'s rows (pixels) [64t, min(rows, 64t + 64)) — or None
+    for a CPU tensor, whose batch norm computes its own statistics."""
+
+    __slots__ = ("partials", "rows", "K", "data_ptr", "shape", "is_cpu")
+
+    def __init__(self, partials, out):
+        B, K, OH, OW = out.shape
+        self.partials = partials
+        self.rows, self.K = B * OH * OW, K
+        self.data_ptr, self.shape = out.data_ptr(), tuple(out.shape)
+        self.is_cpu = not out.is_cuda
+
+
 class _Conv2dNhwcBf16(torch.autograd.Function):
     """conv2d_bf16 on channels-last storage (csrc/conv_nhwc_bf16.hip): the
-    logical shapes are _Conv2dBf16's, activations lie [B][H][W][C]."""
+    logical shapes are _Conv2dBf16's, activations lie [B][H][W][C].  With
+    ``bn_stats`` on a GPU tensor the forward runs the kernel with the
+    statistics epilogue and returns ``(out, partials)``."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, padding, out_dtype):
+    def forward(ctx, x, w, b, stride, padding, out_dtype, bn_stats):
         B, C, H, W = x.shape
         K, _, R, S = w.shape
         (sh, sw), (ph, pw) = stride, padding
@@ -771,10 +793,19 @@ class _Conv2dNhwcBf16(torch.autograd.Function):
                                       w.dtype == torch.float32, False,
                                       _stream())
             out = _empty_nhwc(B, K, OH, OW, x, out_dtype)
-            k.conv2d_nhwc_bf16_fwd(
-                xb.data_ptr(), wp.data_ptr(), _ptr(b), out.data_ptr(),
-                B, C, H, W, K, R, S, sh, sw, ph, pw,
-                out_dtype == torch.float32, _stream())
+            dims = (B, C, H, W, K, R, S, sh, sw, ph, pw)
+            if bn_stats:
+                tiles = k.conv2d_nhwc_bf16_stats_tiles(B * OH * OW)
+                tws = torch.empty(tiles, K, 2, device=x.device,
+                                  dtype=torch.float32)   # fully written
+                k.conv2d_nhwc_bf16_fwd_stats(
+                    xb.data_ptr(), wp.data_ptr(), _ptr(b), out.data_ptr(),
+                    tws.data_ptr(), *dims, out_dtype == torch.float32,
+                    _stream())
+            else:
+                k.conv2d_nhwc_bf16_fwd(
+                    xb.data_ptr(), wp.data_ptr(), _ptr(b), out.data_ptr(),
+                    *dims, out_dtype == torch.float32, _stream())
         else:
             # the default path's arithmetic, so the values are its bits
             xb, w = _to_bf16(x), _to_bf16(w)
@@ -784,10 +815,13 @@ class _Conv2dNhwcBf16(torch.autograd.Function):
         ctx.save_for_backward(xb, w)
         ctx.geom = (stride, padding, OH, OW)
         ctx.has_bias = b is not None
+        if bn_stats and x.is_cuda:
+            ctx.mark_non_differentiable(tws)
+            return out, tws
         return out
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, _g_partials=None):
         xb, w = ctx.saved_tensors
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
@@ -830,7 +864,7 @@ class _Conv2dNhwcBf16(torch.autograd.Function):
                     gw = _to_bf16(gw)
                 if not need_w:
                     gw = None
-            return gx, gw, gb, None, None, None
+            return gx, gw, gb, None, None, None, None
         g = _to_bf16(gy).float()
         if need_x:
             gx = _as_nhwc(torch.nn.grad.conv2d_input(
@@ -840,12 +874,12 @@ class _Conv2dNhwcBf16(torch.autograd.Function):
                 xb.float(), w.shape, g, stride, padding).to(ctx.w_dtype)
         if need_b:
             gb = g.sum(dim=(0, 2, 3))
-        return gx, gw, gb, None, None, None
+        return gx, gw, gb, None, None, None, None
 
 
 def conv2d_bf16(x, w, b=None, stride=1, padding=0,
                 out_dtype=torch.bfloat16,
-                memory_format=torch.contiguous_format):
+                memory_format=torch.contiguous_format, bn_stats=False):
     """2-D convolution (cross-correlation, NCHW) with bf16 operands and
     fp32 accumulation.
 
@@ -864,8 +898,21 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
     brought to [B][H][W][C] storage, which costs nothing where they have it;
     the result and ``gx`` come back with that storage, ``gw`` dense
     [K,C,R,S].  The layout is never taken from ``x``'s strides: any other
-    value than these two raises ``ValueError``."""
+    value than these two raises ``ValueError``.
+
+    ``bn_stats=True`` (channels-last only, else ``ValueError``) is for a
+    convolution whose output goes to a training batch norm.  The call
+    returns ``(out, stats)``: ``out`` and the gradients are bit for bit
+    those of the plain call, and ``stats`` (a ``ConvBatchStats``, not
+    differentiable) holds per-channel partial means and centred second
+    moments of ``out`` as stored — after its one rounding, bias included —
+    which the forward kernel reduced from its own output tiles.
+    ``batchnorm2d(out, ..., batch_stats=stats)`` starts from them instead
+    of reading ``out`` twice.  For CPU tensors ``stats`` is empty."""
     nhwc = _is_nhwc("conv2d_bf16", memory_format)
+    if bn_stats and not nhwc:
+        raise ValueError("conv2d_bf16: bn_stats=True needs "
+                         "memory_format=torch.channels_last")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"conv2d_bf16: out_dtype must be torch.bfloat16 or "
                         f"torch.float32, got {out_dtype}")
@@ -909,7 +956,12 @@ def conv2d_bf16(x, w, b=None, stride=1, padding=0,
         if v >= 2 ** 62:
             raise ValueError(f"conv2d_bf16: {what} has too many elements")
     if nhwc:
-        return _Conv2dNhwcBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
+        res = _Conv2dNhwcBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype,
+                                    bool(bn_stats))
+        if not bn_stats:
+            return res
+        out, partials = res if x.is_cuda else (res, None)
+        return out, ConvBatchStats(partials, out)
     return _Conv2dBf16.apply(x, w, b, (sh, sw), (ph, pw), out_dtype)
 
 
@@ -930,10 +982,12 @@ def _bn_chan(t):
 
 def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
                          training, momentum, eps, residual, fuse_relu,
-                         memory_format=torch.contiguous_format):
+                         memory_format=torch.contiguous_format,
+                         batch_stats=None):
     """The forward of ``batchnorm2d`` on checked tensors, contiguous or,
     with ``memory_format=torch.channels_last``, brought to channels-last
-    storage here.  Returns ``(y, save_mean, save_invstd)``: the fp32 batch
+    storage here.  ``batch_stats`` (checked too) with partials replaces the
+    statistics pass by a merge of those.  Returns ``(y, save_mean, save_invstd)``: the fp32 batch
     statistics the backward uses in training, ``(y, None, None)`` in
     eval."""
     nhwc = _is_nhwc("ops.batchnorm2d", memory_format)
@@ -954,6 +1008,18 @@ def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
         if training:
             mean = torch.empty(C, device=x.device, dtype=torch.float32)
             invstd = torch.empty(C, device=x.device, dtype=torch.float32)
+        if batch_stats is not None and batch_stats.partials is not None:
+            n_ws = k.batchnorm2d_nhwc_merge_ws(*dims)
+            ws = torch.empty(n_ws, device=x.device, dtype=torch.float32) \
+                if n_ws else None
+            k.batchnorm2d_nhwc_fwd_from_partials(
+                x.data_ptr(), _ptr(residual), y.data_ptr(),
+                weight.data_ptr(), bias.data_ptr(), _ptr(running_mean),
+                _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
+                batch_stats.partials.data_ptr(), _ptr(ws), *dims, momentum,
+                eps, fuse_relu, x.dtype == torch.bfloat16, _stream())
+            return y, mean, invstd
+        if training:
             splits = get_splits(*dims)
             ws = torch.empty(C * splits * 3, device=x.device,
                              dtype=torch.float32)
@@ -995,10 +1061,11 @@ def _batchnorm2d_forward(x, weight, bias, running_mean, running_var,
 class _BatchNorm2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var,
-                training, momentum, eps, fuse_relu, memory_format):
+                training, momentum, eps, fuse_relu, memory_format,
+                batch_stats):
         y, mean, invstd = _batchnorm2d_forward(
             x, weight, bias, running_mean, running_var, training, momentum,
-            eps, residual, fuse_relu, memory_format)
+            eps, residual, fuse_relu, memory_format, batch_stats)
         ctx.nhwc = memory_format == torch.channels_last
         if training:
             ctx.save_for_backward(x, weight, mean, invstd,
@@ -1062,12 +1129,13 @@ class _BatchNorm2d(torch.autograd.Function):
                 gx = _as_nhwc(gx) if need_x else None
                 gres = _as_nhwc(gres) if need_r else None
         return (gx, gw if need_w else None, gb if need_b else None, gres,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
                 training=True, momentum=0.1, eps=1e-5, residual=None,
-                fuse_relu=False, memory_format=torch.contiguous_format):
+                fuse_relu=False, memory_format=torch.contiguous_format,
+                batch_stats=None):
     """``relu?(batch_norm(x) + residual?)`` over NCHW in one pass.
 
     ``x`` [B,C,H,W] is fp32 or bf16 and the result has its dtype and shape;
@@ -1090,8 +1158,35 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
     keep their logical [B,C,H,W] shape and are brought to [B][H][W][C]
     storage, which costs nothing where they have it; ``y``, ``gx`` and the
     residual's gradient come back with that storage.  The layout is never
-    taken from ``x``'s strides: any other value raises ``ValueError``."""
+    taken from ``x``'s strides: any other value raises ``ValueError``.
+
+    ``batch_stats`` is the second result of
+    ``conv2d_bf16(..., bn_stats=True)`` and ``x`` that call's first.  The
+    batch statistics are then merged from the convolution's per-tile
+    partials (Chan's formula, fixed order) instead of computed in two
+    passes over ``x``; they are statistics of the same stored values, so
+    the contract above holds unchanged, and the backward is the same.
+    ``ValueError`` unless ``training`` is true, the layout channels-last
+    and ``x`` the tensor (shape and data pointer) the statistics were made
+    for.  On CPU the (empty) ``batch_stats`` is checked and ignored."""
     nhwc = _is_nhwc("ops.batchnorm2d", memory_format)
+    if batch_stats is not None:
+        if not isinstance(batch_stats, ConvBatchStats):
+            raise TypeError("ops.batchnorm2d: batch_stats must come from "
+                            "conv2d_bf16(..., bn_stats=True)")
+        if not training:
+            raise ValueError("ops.batchnorm2d: batch_stats is for "
+                             "training=True; eval uses the running buffers")
+        if not nhwc:
+            raise ValueError("ops.batchnorm2d: batch_stats needs "
+                             "memory_format=torch.channels_last")
+        if not isinstance(x, torch.Tensor) \
+                or tuple(x.shape) != batch_stats.shape \
+                or x.data_ptr() != batch_stats.data_ptr \
+                or x.is_cuda == batch_stats.is_cpu \
+                or (x.is_cuda and _as_nhwc(x).data_ptr() != x.data_ptr()):
+            raise ValueError("ops.batchnorm2d: batch_stats was made for "
+                             "another tensor than x")
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"ops.batchnorm2d: x must be fp32 or bf16, got "
                         f"{x.dtype}")
@@ -1160,7 +1255,7 @@ def batchnorm2d(x, weight, bias, running_mean=None, running_var=None,
     return _BatchNorm2d.apply(
         _laid_out(x, nhwc), weight.contiguous(), bias.contiguous(), residual,
         running_mean, running_var, bool(training), float(momentum),
-        float(eps), bool(fuse_relu), memory_format)
+        float(eps), bool(fuse_relu), memory_format, batch_stats)
 
 
 # ---------------------------------------------------------------------------
