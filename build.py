@@ -69,7 +69,7 @@ def build(force: bool = False, stage_stamps: bool = False):
                             "conv_nhwc_bf16.hip",
                             "batchnorm.hip", "pool.hip",
                             "cross_entropy.hip"),
-         src("batchnorm_nhwc.hip", "pool_nhwc.hip"),
+         src("batchnorm_nhwc.hip", "pool_nhwc.hip", "linear_fp8.hip"),
          src("common.h", "gemm_bf16.h", "bn_shared.h", "pool_shared.h",
              "nhwc_tile.h"), []),
     ]

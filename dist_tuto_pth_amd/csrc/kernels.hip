@@ -803,6 +803,7 @@ void copy_throttled(uintptr_t dst, uintptr_t src, int64_t n, int nblocks,
 void register_pointwise(pybind11::module_& m);
 void register_net_fused(pybind11::module_& m);
 void register_linear_bf16(pybind11::module_& m);
+void register_linear_fp8(pybind11::module_& m);
 void register_conv_bf16(pybind11::module_& m);
 void register_conv_nhwc_bf16(pybind11::module_& m);
 void register_batchnorm(pybind11::module_& m);
@@ -839,6 +840,7 @@ PYBIND11_MODULE(_kernels, m) {
   register_pointwise(m);
   register_net_fused(m);
   register_linear_bf16(m);
+  register_linear_fp8(m);
   register_conv_bf16(m);
   register_conv_nhwc_bf16(m);
   register_batchnorm(m);

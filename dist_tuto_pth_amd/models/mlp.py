@@ -26,17 +26,23 @@ class MLP(nn.Module):
     and their gradients stay fp32, every layer runs `ops.linear_bf16`
     (bf16 operands on the matrix cores, fp32 accumulation), hidden
     activations and dropout are bf16, and the last layer returns fp32
-    logits so the loss kernels are the fp32 ones."""
+    logits so the loss kernels are the fp32 ones.
+
+    ``compute_dtype=torch.float8_e4m3fn`` is the same arrangement on
+    `ops.linear_fp8`: operands quantised to fp8 per tensor on the 128-deep
+    matrix instruction, bf16 hidden activations and dropout, fp32 logits,
+    fp32 parameters and gradients under the same names, so a ``state_dict``
+    moves between all three modes."""
 
     def __init__(self, widths: Sequence[int] = (784, 256, 128, 10),
                  dropout: float = 0.2,
                  compute_dtype: Optional[torch.dtype] = None):
         super().__init__()
         assert len(widths) >= 2
-        if compute_dtype not in (None, torch.bfloat16):
+        if compute_dtype not in (None, torch.bfloat16, torch.float8_e4m3fn):
             raise ValueError(
-                f"MLP: compute_dtype must be None or torch.bfloat16, "
-                f"got {compute_dtype}")
+                f"MLP: compute_dtype must be None, torch.bfloat16 or "
+                f"torch.float8_e4m3fn, got {compute_dtype}")
         self.compute_dtype = compute_dtype
         self.widths = list(widths)
         self.p = dropout
@@ -48,7 +54,10 @@ class MLP(nn.Module):
         for i, lin in enumerate(self.layers):
             last = i == len(self.layers) - 1
             if self.compute_dtype is not None:
-                x = ops.linear_bf16(
+                lin_op = ops.linear_bf16 \
+                    if self.compute_dtype == torch.bfloat16 \
+                    else ops.linear_fp8
+                x = lin_op(
                     x, lin.weight, lin.bias, fuse_relu=not last,
                     out_dtype=torch.float32 if last else torch.bfloat16)
             else:

@@ -3,7 +3,7 @@
 Every op the reference's ``Net.forward`` + SGD step trigger implicitly
 through torch (train_dist.py:58-71,110,118-124) is a hand-written CDNA4
 HIP kernel here, with forward *and* backward (``csrc/kernels.hip``; K3-K6
-in ``csrc/pointwise.hip``, K16-K21 in the files named at their sections):
+in ``csrc/pointwise.hip``, K16-K22 in the files named at their sections):
 
   K1/K2  conv2d (direct, LDS-tiled)        -> conv2d
   K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu (fp32, bf16)
@@ -12,6 +12,7 @@ in ``csrc/pointwise.hip``, K16-K21 in the files named at their sections):
                                               (fp32, bf16)
   K7/K8  linear (+fused ReLU epilogue)     -> linear
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
+  K22    fp8 (e4m3/e5m2) 128-deep MFMA linear -> linear_fp8, quantize_fp8
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
          the same on channels-last storage  -> conv2d_bf16(memory_format=
                                               torch.channels_last)
@@ -598,6 +599,215 @@ def linear_bf16(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
             raise ValueError("linear_bf16: b must have shape [N]")
         b = b.contiguous()
     return _LinearBf16.apply(x, w, b, fuse_relu, out_dtype)
+
+
+# ---------------------------------------------------------------------------
+# K22 — fp8 linear on the 128-deep fp8 matrix instruction
+# (csrc/linear_fp8.hip).  Contract, on GPU and CPU alike: per-tensor,
+# current, power-of-two scaling; x and w quantised to e4m3, the incoming
+# gradient to e5m2, each RNE from the exactly scaled value; exact products
+# summed in fp32; the sum multiplied by the exact inverse scales, bias added
+# in fp32, ReLU, one rounding to the output dtype.
+# ---------------------------------------------------------------------------
+_FP8_E = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 15}   # FMAX = 1.75 * 2^E
+
+
+def _fp8_quantize_cpu(t, dtype):
+    """``quantize_fp8``'s rule with torch ops: the executable statement of
+    the contract.  Returns ``(q, s)`` with ``s`` a 0-dim fp32 tensor."""
+    amax = t.detach().abs().max().float()
+    m, ex = torch.frexp(amax)            # amax = m * 2^ex, m in [0.5, 1)
+    # amax = f * 2^e with f = 2m in [1, 2), e = ex - 1
+    k = _FP8_E[dtype] - (ex - 1) - (m > 0.875).to(ex.dtype)
+    k = torch.where(amax == 0, torch.zeros_like(k), k.clamp(-126, 126))
+    s = torch.ldexp(torch.ones((), dtype=torch.float32), k)
+    return (t.detach().float() * s).to(dtype), s
+
+
+def _fp8_quantize_gpu(t, dtype, mask=None, want_q=True, want_qT=False,
+                      want_gb=False):
+    """Quantise the dense 2-D CUDA tensor ``t`` (fp32 or bf16), zeroed where
+    ``mask <= 0``.  Returns ``(q, qT, ws, gb)``: the padded row-major and
+    transposed uint8 storages (None where not wanted), the fp32 workspace
+    whose first two elements are ``s`` and ``1/s``, and the fp32 column sums
+    of the masked ``t``."""
+    k = _k()
+    R, C = t.shape
+    dev = t.device
+    q = torch.empty(R, k.fp8_pitch(C), device=dev, dtype=torch.uint8) \
+        if want_q else None
+    qT = torch.empty(C, k.fp8_pitch(R), device=dev, dtype=torch.uint8) \
+        if want_qT else None
+    ws = torch.empty(k.fp8_ws_floats(), device=dev, dtype=torch.float32)
+    gb = gb_part = None
+    if want_gb:
+        gb = torch.empty(C, device=dev, dtype=torch.float32)
+        gb_part = torch.empty(k.fp8_pitch(R) // 64 * C, device=dev,
+                              dtype=torch.float32)
+    k.fp8_quantize(t.data_ptr(), t.dtype == torch.bfloat16, _ptr(mask),
+                   mask is not None and mask.dtype == torch.float32, R, C,
+                   dtype == torch.float8_e5m2, _ptr(q), _ptr(qT),
+                   ws.data_ptr(), _ptr(gb_part), _ptr(gb), _stream())
+    return q, qT, ws, gb
+
+
+def quantize_fp8(t, dtype):
+    """Quantise ``t`` (fp32 or bf16, at least 1-D, no empty dimension) to
+    ``dtype`` (``torch.float8_e4m3fn`` or ``torch.float8_e5m2``) with one
+    power-of-two scale for the whole tensor.  Returns ``(q, scale)``.
+
+    With ``amax = max|t| = f * 2^e``, ``f`` in [1, 2), the scale is
+    ``2^k``, ``k = E - e`` for ``f <= 1.75`` and ``E - 1 - e`` otherwise
+    (``E`` = 8 for e4m3, 15 for e5m2): the largest power of two with
+    ``amax * scale <= FMAX``.  ``k`` is clamped to [-126, 126] and is 0 for
+    ``amax == 0``; non-finite input is outside the contract.  ``q`` is
+    ``RNE(t * scale)``, bit for bit torch's CPU cast of that product; it has
+    ``t``'s shape and, on GPU, is a view of the kernel's storage, whose rows
+    are zero-padded to a multiple of 128 bytes.  ``scale`` is a 0-dim fp32
+    tensor on ``t``'s device; nothing is read back to the host."""
+    if dtype not in _FP8_E:
+        raise TypeError(f"quantize_fp8: dtype must be torch.float8_e4m3fn or "
+                        f"torch.float8_e5m2, got {dtype}")
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32,
+                                                          torch.bfloat16):
+        raise TypeError("quantize_fp8: t must be an fp32 or bf16 tensor")
+    if t.dim() < 1 or min(t.shape) < 1:
+        raise ValueError(f"quantize_fp8: t must have at least one dimension "
+                         f"and none empty, got {tuple(t.shape)}")
+    if not t.is_cuda:
+        return _fp8_quantize_cpu(t, dtype)
+    t2 = t.detach().contiguous().view(-1, t.shape[-1])
+    q, _, ws, _ = _fp8_quantize_gpu(t2, dtype)
+    return q[:, :t.shape[-1]].view(dtype).reshape(t.shape), ws[0]
+
+
+class _LinearFp8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, fuse_relu, out_dtype):
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        B, K = x.shape
+        N = w.shape[0]
+        e4m3 = torch.float8_e4m3fn
+        if x.is_cuda:
+            k = _k()
+            # each operand is quantised once per step: the transposed copies
+            # the backward needs come out of the same pass
+            xq, xqT, sx, _ = _fp8_quantize_gpu(
+                x.detach().contiguous(), e4m3, want_qT=need_w)
+            wq, wqT, sw, _ = _fp8_quantize_gpu(
+                w.detach().contiguous(), e4m3, want_qT=need_x)
+            out = torch.empty(B, N, device=x.device, dtype=out_dtype)
+            k.linear_fp8_fwd(xq.data_ptr(), wq.data_ptr(), sx.data_ptr(),
+                             sw.data_ptr(), _ptr(b), out.data_ptr(), B, K, N,
+                             fuse_relu, out_dtype == torch.float32,
+                             _stream())
+            ctx.save_for_backward(xqT, wqT, sx, sw,
+                                  out if fuse_relu else None)
+        else:
+            xq, sx = _fp8_quantize_cpu(x.detach(), e4m3)
+            wq, sw = _fp8_quantize_cpu(w.detach(), e4m3)
+            acc = (xq.float() @ wq.float().t()) * (1.0 / sx) * (1.0 / sw)
+            if b is not None:
+                acc = acc + b
+            if fuse_relu:
+                acc = F.relu(acc)
+            out = acc.to(out_dtype)
+            ctx.save_for_backward(xq, wq, sx, sw, out if fuse_relu else None)
+        ctx.dims = (B, K, N)
+        ctx.x_dtype, ctx.w_dtype = x.dtype, w.dtype
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, ws_, sx, sw, out = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        B, K, N = ctx.dims
+        e5m2 = torch.float8_e5m2
+        gx = gw = gb = None
+        if gy.is_cuda:
+            k = _k()
+            dev = gy.device
+            gq, gqT, sg, gb = _fp8_quantize_gpu(
+                gy.contiguous(), e5m2, mask=out, want_q=need_x,
+                want_qT=need_w or not need_x, want_gb=need_b)
+            if need_x:
+                gx = torch.empty(B, K, device=dev, dtype=ctx.x_dtype)
+                k.linear_fp8_bwd_x(gq.data_ptr(), ws_.data_ptr(),
+                                   sg.data_ptr(), sw.data_ptr(),
+                                   gx.data_ptr(), B, K, N,
+                                   ctx.x_dtype == torch.float32, _stream())
+            if need_w:
+                gw = torch.empty(N, K, device=dev, dtype=torch.float32)
+                splits = k.linear_fp8_gw_splits(B, K, N)
+                part = torch.empty(splits * N * K, device=dev,
+                                   dtype=torch.float32) \
+                    if splits > 1 else None
+                k.linear_fp8_bwd_w(gqT.data_ptr(), xs.data_ptr(),
+                                   sg.data_ptr(), sx.data_ptr(),
+                                   gw.data_ptr(), _ptr(part), splits,
+                                   B, K, N, _stream())
+                if ctx.w_dtype == torch.bfloat16:
+                    gw = _to_bf16(gw)
+            return gx, gw, gb, None, None
+        g = gy.float()
+        if out is not None:
+            g = torch.where(out > 0, g, torch.zeros_like(g))
+        gq, sg = _fp8_quantize_cpu(g, e5m2)
+        if need_x:
+            gx = ((gq.float() @ ws_.float()) * (1.0 / sg)
+                  * (1.0 / sw)).to(ctx.x_dtype)
+        if need_w:
+            gw = ((gq.float().t() @ xs.float()) * (1.0 / sg)
+                  * (1.0 / sx)).to(ctx.w_dtype)
+        if need_b:
+            gb = g.sum(0)
+        return gx, gw, gb, None, None
+
+
+def linear_fp8(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
+    """``relu?(x @ w.T + b)`` with fp8 operands and fp32 accumulation.
+
+    ``x`` [B,K] and ``w`` [N,K] are fp32 or bf16, ``b`` is fp32 or None;
+    the result is [B,N] in ``out_dtype`` (bf16 or fp32).  ``x`` and ``w``
+    are quantised to e4m3 and, in backward, the incoming gradient to e5m2,
+    each with its own power-of-two scale of the current tensor
+    (``quantize_fp8``'s rule; scales stay on the device).  Products are
+    exact in fp32 and are summed in fp32; the sum is multiplied by the exact
+    inverse scales, the bias added, ReLU applied, and the result rounded
+    once.  With ``fuse_relu`` the gradient is zeroed where ``out <= 0``
+    before it is quantised, so its scale is the masked gradient's.  On the
+    GPU the sum is the matrix instruction's, which drops a product 2^-14 or
+    more below the largest one it is first added to
+    (profiles/linear_fp8_numbers.md); it is deterministic all the same.
+
+    Backward gives ``gx`` in ``x``'s dtype, ``gw`` in fp32 for an fp32
+    (master) weight or rounded once to bf16 for a bf16 weight, and ``gb``
+    in fp32 — the column sum of the masked, *unquantised* gradient.  ``gw``
+    and ``gb`` are bitwise reproducible.  CPU tensors run the same contract
+    with torch's float8 casts and an fp32 matmul."""
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"linear_fp8: out_dtype must be torch.bfloat16 or "
+                        f"torch.float32, got {out_dtype}")
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"linear_fp8: x [B,K] and w [N,K] expected, got "
+                         f"{tuple(x.shape)} and {tuple(w.shape)}")
+    if min(x.shape[0], x.shape[1], w.shape[0]) < 1:
+        raise ValueError("linear_fp8: B, K and N must be >= 1")
+    for name, t in (("x", x), ("w", w)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"linear_fp8: {name} must be fp32 or bf16, "
+                            f"got {t.dtype}")
+    if w.device != x.device:
+        raise ValueError(f"linear_fp8: w is on {w.device}, x on {x.device}")
+    if b is not None:
+        if b.dtype != torch.float32:
+            raise TypeError(f"linear_fp8: b must be fp32, got {b.dtype}")
+        if b.shape != (w.shape[0],):
+            raise ValueError("linear_fp8: b must have shape [N]")
+        b = b.contiguous()
+    return _LinearFp8.apply(x, w, b, bool(fuse_relu), out_dtype)
 
 
 # ---------------------------------------------------------------------------
