@@ -14,7 +14,13 @@ measurements, in microseconds.  A second table gives the MLP training step
 in its three modes.  --probe prints what the 128-deep instruction keeps of
 small terms next to a large one.
 
-Run on a GPU box:  python benchmarks/bench_linear_fp8.py [--probe]
+--scaling mx compares K23's MXFP8 path with the per-tensor path instead of
+bf16: `tensor +q` / `mx +q` and `tensor` / `mx` (GEMM alone) per product, and
+the MLP step in bf16, fp8 per-tensor and fp8 MX.  With it, --probe prints
+which stored scale byte the scaled instruction applies to which data.
+
+Run on a GPU box:
+    python benchmarks/bench_linear_fp8.py [--scaling mx] [--probe]
 """
 
 import argparse
@@ -132,11 +138,65 @@ def layer_fns(B, K, N, dev):
             ("gw", (gw8q, gw8, gw16))]
 
 
-def mlp_step_fns(batch, dev):
+def mx_layer_fns(B, K, N, dev):
+    """per product: (tensor +q, mx +q, tensor, mx); the per-tensor entries
+    are layer_fns' own"""
+    k = load_native("_kernels")
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(B, K, generator=g).bfloat16().to(dev)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev)
+    b = torch.randn(N, generator=g).to(dev)
+    gy = torch.randn(B, N, generator=g).bfloat16().to(dev)
+    out = torch.empty(B, N, device=dev, dtype=torch.bfloat16)
+    gx = torch.empty(B, K, device=dev, dtype=torch.bfloat16)
+    gw = torch.empty(N, K, device=dev)
+    quant = ops._mxfp8_quantize_gpu
+    xq, sx, xqT, sxT, _ = quant(x, E4M3, want_qT=True)
+    wq, sw, wqT, swT, _ = quant(w, E4M3, want_qT=True)
+    gq, sg, gqT, sgT, _ = quant(gy, E5M2, want_qT=True)
+    s8 = k.linear_fp8_gw_splits(B, K, N)
+    p8 = torch.empty(s8 * N * K, device=dev)
+
+    def fwd():
+        k.linear_mxfp8_fwd(xq.data_ptr(), wq.data_ptr(), sx.data_ptr(),
+                           sw.data_ptr(), b.data_ptr(), out.data_ptr(), B, K,
+                           N, True, False, st)
+
+    def fwdq():
+        quant(x, E4M3, want_qT=True)
+        quant(w, E4M3, want_qT=True)
+        fwd()
+
+    def gxf():
+        k.linear_mxfp8_bwd_x(gq.data_ptr(), wqT.data_ptr(), sg.data_ptr(),
+                             swT.data_ptr(), gx.data_ptr(), B, K, N, False, st)
+
+    def gxq():
+        quant(gy, E5M2, mask=out)
+        gxf()
+
+    def gwf():
+        k.linear_mxfp8_bwd_w(gqT.data_ptr(), xqT.data_ptr(), sgT.data_ptr(),
+                             sxT.data_ptr(), gw.data_ptr(), p8.data_ptr(), s8,
+                             B, K, N, st)
+
+    def gwq():
+        quant(gy, E5M2, mask=out, want_q=False, want_qT=True, want_gb=True)
+        gwf()
+
+    mx = [(fwdq, fwd), (gxq, gxf), (gwq, gwf)]
+    return [(name, (t[0], m[0], t[1], m[1]))
+            for (name, t), m in zip(layer_fns(B, K, N, dev), mx)]
+
+
+def mlp_step_fns(batch, dev, modes=((None, "tensor"),
+                                    (torch.bfloat16, "tensor"),
+                                    (E4M3, "tensor"))):
     fns = []
-    for mode in (None, torch.bfloat16, E4M3):
+    for mode, scaling in modes:
         torch.manual_seed(0)
-        model = MLP(compute_dtype=mode).to(dev)
+        model = MLP(compute_dtype=mode, fp8_scaling=scaling).to(dev)
         opt = FusedSGD(model.parameters(), lr=0.01, momentum=0.5)
         x = torch.randn(batch, 784, device=dev)
         tgt = torch.randint(0, 10, (batch,), device=dev)
@@ -173,15 +233,74 @@ def probe(dev):
               % (m, got, float(exact[i]), (got - 2.0 ** 15) / 2.0 ** (15 - m)))
 
 
+def probe_mx(dev):
+    """Which stored scale byte does the instruction apply to which data?
+    (B, K, N) = (16, 128, 16), one instruction per fragment.  The probed
+    operand's byte at (row r, block c) is 127 + 4r + c, the other operand's
+    are 127; elements are 1 in one k block at a time and 0 elsewhere, so
+    every result is 32 * 2^code of the byte that was applied."""
+    k = load_native("_kernels")
+    st = torch.cuda.current_stream().cuda_stream
+    one = int(torch.ones(()).to(E4M3).view(torch.uint8))
+    codes = (127 + torch.arange(64).view(16, 4)).to(torch.uint8).to(dev)
+    unit = torch.full((16, 4), 127, dtype=torch.uint8, device=dev)
+    ones = torch.full((16, 128), one, dtype=torch.uint8, device=dev)
+    c = torch.empty(16, 16, device=dev)
+    for side in ("A (x, second source)", "B (w, first source)"):
+        wrong = 0
+        for kb in range(4):
+            data = torch.zeros(16, 128, dtype=torch.uint8, device=dev)
+            data[:, 32 * kb:32 * kb + 32] = one
+            a, sa, b, sb = (data, codes, ones, unit) if side[0] == "A" \
+                else (ones, unit, data, codes)
+            k.linear_mxfp8_fwd(a.data_ptr(), b.data_ptr(), sa.data_ptr(),
+                               sb.data_ptr(), 0, c.data_ptr(), 16, 128, 16,
+                               False, True, st)
+            code = torch.log2(c / 32).cpu()       # [m][n]
+            code = code if side[0] == "A" else code.t()
+            for r in range(16):
+                got = sorted(set(code[r].tolist()))
+                ok = got == [4.0 * r + kb]
+                wrong += not ok
+                if not ok or r in (0, 5, 15):
+                    print("%s: data at row %2d, k block %d scaled by the byte "
+                          "stored at %s" % (side, r, kb, [
+                              "(row %d, block %d)" % divmod(int(v), 4)
+                              if v == int(v) and 0 <= v < 64 else repr(v)
+                              for v in got]))
+        print("%s: %d of 64 (row, block) pairs off the identity mapping"
+              % (side, wrong))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--probe", action="store_true")
+    ap.add_argument("--scaling", choices=("tensor", "mx"), default="tensor")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     dev = torch.device("cuda:0")
     load_native("_kernels")
     if args.probe:
-        return probe(dev)
+        return probe_mx(dev) if args.scaling == "mx" else probe(dev)
+    if args.scaling == "mx":
+        print("| B | K | N | product | tensor +q us | mx +q us | tensor us "
+              "| mx us |")
+        print("|---|---|---|---|---|---|---|---|")
+        for B, K, N in SHAPES:
+            reps = 20 if 2.0 * B * K * N > 1e10 else 200
+            for name, fns in mx_layer_fns(B, K, N, dev):
+                cells = alternate(fns, reps)
+                print("| %d | %d | %d | %s | %s |"
+                      % (B, K, N, name, " | ".join(cells)), flush=True)
+        print()
+        print("| MLP 784-256-128-10 step, batch | bf16 us | fp8 tensor us "
+              "| fp8 mx us |")
+        print("|---|---|---|---|")
+        modes = ((torch.bfloat16, "tensor"), (E4M3, "tensor"), (E4M3, "mx"))
+        for batch in (128, 4096):
+            cells = alternate(mlp_step_fns(batch, dev, modes), 100)
+            print("| %d | %s |" % (batch, " | ".join(cells)), flush=True)
+        return
 
     print("| B | K | N | product | fp8 +q us | fp8 us | bf16 us |")
     print("|---|---|---|---|---|---|---|")

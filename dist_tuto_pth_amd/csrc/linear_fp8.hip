@@ -57,6 +57,34 @@
 //     buffer that gemm_bf16.h's gw_combine_kernel sums in split order: no
 //     float atomics, bitwise reproducible.
 //
+// K23 — MXFP8: the same GEMM with the instruction's block scales in use.
+// A block is 32 consecutive elements along the reduction axis, completed
+// with zeros; its scale 2^k follows the rule above from the block's own amax
+// and is stored as the e8m0 byte 127 - k of the decode factor 2^-k (in
+// [1, 253]).  The instruction multiplies a block's products by both decode
+// factors, so the accumulator is the result and the epilogue has no inverse
+// scale.
+//   mxfp8_quant_kernel  one launch per tensor, no amax pass: the 64x64 tile
+//                 of cast_kernel, but every 32-block is scaled on its own.
+//                 Along a row the 8 lanes that hold a block exchange their
+//                 amax by three xor shuffles.  Along a column a block is 8
+//                 thread rows = two waves: two shuffles inside the wave, then
+//                 one LDS row per wave.  The transposed copy is cast from the
+//                 source with the column scales, so it is not the transpose
+//                 of the row copy.  Scale bytes leave as one 16-bit store per
+//                 tile row: sq[R][pad128(C)/32], sqT[C][pad128(R)/32].
+//                 Padding is byte 0x00 with scale 127, from the same blocks.
+//   gemm_fp8_kernel<.., MX>  the instruction scales its k = 32g..32g+31 of
+//                 row (lane & 15) by the byte that lane 16g + (lane & 15)
+//                 passes, and a lane's two 16-byte register halves are its
+//                 k = 16g.. and 64+16g.., g = lane >> 4 (measured:
+//                 profiles/linear_mxfp8_numbers.md).  So the MX fragment is
+//                 those two 16-byte LDS reads, not 32 consecutive bytes, and
+//                 lane group g carries the scale of the row's block g.  The
+//                 lane loads that byte of the NEXT k tile straight to a
+//                 register together with the operand loads, under the MFMAs;
+//                 rows out of range read 127.
+//
 // Bindings are registered from kernels.hip's PYBIND11_MODULE through
 // register_linear_fp8().
 
@@ -252,6 +280,131 @@ __global__ __launch_bounds__(BLK) void fp8_cast_kernel(
   }
 }
 
+// 2^k for one block from its amax bits; byte is the e8m0 code of 2^-k
+template <bool E5M2>
+__device__ __forceinline__ float mx_scale(uint32_t amax, uint32_t& byte) {
+  const int k = scale_exp(amax, E5M2 ? 15 : 8);
+  byte = (uint32_t)(127 - k);
+  return __uint_as_float((uint32_t)(k + 127) << 23);
+}
+
+// K23's quantiser: grid and tile as fp8_cast_kernel.  sq / sqT are the e8m0
+// scales of q / qT, ldq / 32 and ldqT / 32 bytes per row.
+template <typename T, bool E5M2>
+__global__ __launch_bounds__(BLK) void mxfp8_quant_kernel(
+    const T* __restrict__ src, const void* __restrict__ mask, int mask_f32,
+    int R, int C, int vec, uint8_t* __restrict__ q, uint8_t* __restrict__ sq,
+    int64_t ldq, uint8_t* __restrict__ qT, uint8_t* __restrict__ sqT,
+    int64_t ldqT, float* __restrict__ gb_part) {
+  __shared__ __attribute__((aligned(16))) uint32_t Qs[QT][QP];
+  __shared__ __attribute__((aligned(16))) uint32_t QTs[QT][QP];
+  __shared__ float Gs[QT / 4][QT];
+  __shared__ uint32_t Cm[NWAVE][QT];  // column amax over each wave's 16 rows
+  __shared__ __attribute__((aligned(4))) uint8_t Sr[QT][2], Sc[QT][2];
+
+  const int tid = threadIdx.x;
+  const int tx = tid & 15, ty = tid >> 4, wave = tid >> 6;
+  const int r0 = blockIdx.x * QT + ty * 4, c0 = blockIdx.y * QT + tx * 4;
+  float f[4][4];
+  uint32_t rm[4] = {0u, 0u, 0u, 0u}, cm[4] = {0u, 0u, 0u, 0u};
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = r0 + i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[i][j] = 0.f;
+    if (r < R) {
+      const int64_t at = (int64_t)r * C + c0;
+      if (vec && c0 < C) {  // vec: C % 4 == 0, so the 4 are in range
+        masked4(src, mask, mask_f32, at, f[i]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c0 + j < C) f[i][j] = masked1(src, mask, mask_f32, at + j);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t a = __float_as_uint(f[i][j]) & 0x7fffffffu;
+      cs[j] += f[i][j];
+      rm[i] = max(rm[i], a);
+      cm[j] = max(cm[j], a);
+    }
+  }
+
+  if (q) {  // a row block is the 8 lanes tx & ~7 .. of one thread row
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int o = 1; o < 8; o <<= 1)
+        rm[i] = max(rm[i], (uint32_t)__shfl_xor((int)rm[i], o, 64));
+      uint32_t byte;
+      const float s = mx_scale<E5M2>(rm[i], byte);
+      Qs[ty * 4 + i][tx] =
+          cvt4<E5M2>(f[i][0] * s, f[i][1] * s, f[i][2] * s, f[i][3] * s);
+      if ((tx & 7) == 0) Sr[ty * 4 + i][tx >> 3] = (uint8_t)byte;
+    }
+  }
+  if (qT) {  // a column block is 8 thread rows: this wave's 4 and its pair's
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      cm[j] = max(cm[j], (uint32_t)__shfl_xor((int)cm[j], 16, 64));
+      cm[j] = max(cm[j], (uint32_t)__shfl_xor((int)cm[j], 32, 64));
+      if ((ty & 3) == 0) Cm[wave][tx * 4 + j] = cm[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t byte;
+      const float s =
+          mx_scale<E5M2>(max(cm[j], Cm[wave ^ 1][tx * 4 + j]), byte);
+      // column c0 + j of the patch, rows r0..r0+3
+      QTs[tx * 4 + j][ty] =
+          cvt4<E5M2>(f[0][j] * s, f[1][j] * s, f[2][j] * s, f[3][j] * s);
+      if ((ty & 7) == 0) Sc[tx * 4 + j][ty >> 3] = (uint8_t)byte;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) Gs[ty][tx * 4 + j] = cs[j];
+  __syncthreads();
+
+  const int row = tid >> 2, seg = tid & 3;  // 16 bytes of one tile row
+  if (q) {
+    const int r = blockIdx.x * QT + row;
+    if (r < R)
+      *reinterpret_cast<uint4*>(q + (int64_t)r * ldq + blockIdx.y * QT +
+                                seg * 16) =
+          *reinterpret_cast<const uint4*>(&Qs[row][seg * 4]);
+    if (tid < QT && blockIdx.x * QT + tid < R)
+      *reinterpret_cast<uint16_t*>(sq +
+                                   (int64_t)(blockIdx.x * QT + tid) *
+                                       (ldq / 32) +
+                                   blockIdx.y * 2) =
+          *reinterpret_cast<const uint16_t*>(Sr[tid]);
+  }
+  if (qT) {
+    const int c = blockIdx.y * QT + row;
+    if (c < C)
+      *reinterpret_cast<uint4*>(qT + (int64_t)c * ldqT + blockIdx.x * QT +
+                                seg * 16) =
+          *reinterpret_cast<const uint4*>(&QTs[row][seg * 4]);
+    const int t = tid - QT;  // the second wave writes the scales
+    if (t >= 0 && t < QT && blockIdx.y * QT + t < C)
+      *reinterpret_cast<uint16_t*>(sqT +
+                                   (int64_t)(blockIdx.y * QT + t) *
+                                       (ldqT / 32) +
+                                   blockIdx.x * 2) =
+          *reinterpret_cast<const uint16_t*>(Sc[t]);
+  }
+  if (gb_part && tid < QT) {
+    const int c = blockIdx.y * QT + tid;
+    float sum = 0.f;
+#pragma unroll
+    for (int y = 0; y < QT / 4; ++y) sum += Gs[y][tid];
+    if (c < C) gb_part[(int64_t)blockIdx.x * C + c] = sum;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // the GEMM
 // ---------------------------------------------------------------------------
@@ -260,6 +413,7 @@ struct Fp8Operand {
   int64_t ld;              // bytes, a multiple of 16; k is padded to 128
   int rows;                // valid r in [0, rows)
   const float* inv_scale;  // 1/s of this tensor, in device memory
+  const uint8_t* sc;       // MX: e8m0 block scales, ld / 32 bytes per row
 };
 
 // this thread's two 16-byte chunks of the tile rows [r0, r0+64) x bytes
@@ -286,19 +440,40 @@ __device__ __forceinline__ void lstore(uint8_t (*T)[PITCH], int tid,
   }
 }
 
+// MX: the instruction's k index of a lane's register half h is
+// 64*h + 16*(lane >> 4) + byte, and lane group g's scale byte goes to k
+// 32*g .. 32*g+31 (measured).  So the lane reads bytes 16*g.. and 64+16*g..
+// of its row, and block g of the row is scaled by the byte lane group g holds.
+// Without block scales the order within the sum is free and the lane keeps
+// its 32 consecutive bytes.
+template <bool MX>
 __device__ __forceinline__ frag_f8 lfrag(const uint8_t (*T)[PITCH], int row,
                                          int lane) {
-  const uint4* p =
-      reinterpret_cast<const uint4*>(&T[row + (lane & 15)][32 * (lane >> 4)]);
-  const uint4 lo = p[0], hi = p[1];
+  const uint4* p = reinterpret_cast<const uint4*>(
+      &T[row + (lane & 15)][(MX ? 16 : 32) * (lane >> 4)]);
+  const uint4 lo = p[0], hi = p[MX ? 4 : 1];
   return frag_f8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w,
                  (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
 }
 
+// MX: this lane's scale bytes for its fragments of the tile rows r0 + 16*i,
+// k tile k0: row (lane & 15), block (lane >> 4); 127 (2^0) out of range
+__device__ __forceinline__ void sload(const Fp8Operand& o, int r0, int k0,
+                                      int lane, int (&s)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + i * 16 + (lane & 15);
+    s[i] = r < o.rows
+               ? (int)o.sc[(int64_t)r * (o.ld >> 5) + (k0 >> 5) + (lane >> 4)]
+               : 127;
+  }
+}
+
 // grid = (m tiles, n tiles, splits); split z reduces the k bytes
 // [z*kchunk, min(Kred, (z+1)*kchunk)) into C + z*M*N.  Kred and kchunk are
-// multiples of 128.  A is e5m2 if A_E5M2, else e4m3; B is e4m3.
-template <bool A_E5M2, typename OutT>
+// multiples of 128.  A is e5m2 if A_E5M2, else e4m3; B is e4m3.  MX: the
+// operands carry block scales and no per-tensor inverse scale.
+template <bool A_E5M2, bool MX, typename OutT>
 __global__ __launch_bounds__(BLK) void gemm_fp8_kernel(
     Fp8Operand A, Fp8Operand B, int Kred, int kchunk, OutT* __restrict__ C,
     const float* __restrict__ bias, int relu, int vec_out) {
@@ -320,9 +495,14 @@ __global__ __launch_bounds__(BLK) void gemm_fp8_kernel(
     for (int j = 0; j < 2; ++j) acc[i][j] = frag_cd{0.f, 0.f, 0.f, 0.f};
 
   uint4 ra[2], rb[2];
+  int sa[2] = {127, 127}, sb[2] = {127, 127}, na[2], nb[2];
   if (kbeg < kend) {
     gload(A, m0, kbeg, tid, ra);
     gload(B, n0, kbeg, tid, rb);
+    if constexpr (MX) {
+      sload(A, m0 + wm, kbeg, lane, sa);
+      sload(B, n0 + wn, kbeg, lane, sb);
+    }
     lstore(As[0], tid, ra);
     lstore(Bs[0], tid, rb);
   }
@@ -333,12 +513,16 @@ __global__ __launch_bounds__(BLK) void gemm_fp8_kernel(
     if (more) {  // next tile's global loads fly under the MFMAs
       gload(A, m0, k0 + TK, tid, ra);
       gload(B, n0, k0 + TK, tid, rb);
+      if constexpr (MX) {
+        sload(A, m0 + wm, k0 + TK, lane, na);
+        sload(B, n0 + wn, k0 + TK, lane, nb);
+      }
     }
     frag_f8 a[2], b[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      a[i] = lfrag(As[buf], wm + i * 16, lane);
-      b[i] = lfrag(Bs[buf], wn + i * 16, lane);
+      a[i] = lfrag<MX>(As[buf], wm + i * 16, lane);
+      b[i] = lfrag<MX>(Bs[buf], wn + i * 16, lane);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -346,16 +530,26 @@ __global__ __launch_bounds__(BLK) void gemm_fp8_kernel(
       for (int j = 0; j < 2; ++j)
         // B first: the accumulator's 4 registers run along n.  Format
         // selectors: 0 = e4m3, 1 = e5m2; 127 is the block scale 2^0.
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            b[j], a[i], acc[i][j], 0, A_E5M2 ? 1 : 0, 0, 127, 0, 127);
+        // MX: byte 0 of the lane's scale register, for block lane >> 4.
+        if constexpr (MX)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              b[j], a[i], acc[i][j], 0, A_E5M2 ? 1 : 0, 0, sb[j], 0, sa[i]);
+        else
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              b[j], a[i], acc[i][j], 0, A_E5M2 ? 1 : 0, 0, 127, 0, 127);
     if (more) {  // the other buffer was last read before the previous barrier
       lstore(As[buf ^ 1], tid, ra);
       lstore(Bs[buf ^ 1], tid, rb);
+      if constexpr (MX) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) sa[i] = na[i], sb[i] = nb[i];
+      }
     }
     __syncthreads();
   }
 
-  const float inv_a = *A.inv_scale, inv_b = *B.inv_scale;
+  float inv_a = 1.f, inv_b = 1.f;
+  if constexpr (!MX) inv_a = *A.inv_scale, inv_b = *B.inv_scale;
   OutT* Cz = C + (int64_t)blockIdx.z * M * N;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -369,7 +563,7 @@ __global__ __launch_bounds__(BLK) void gemm_fp8_kernel(
       for (int r = 0; r < 4; ++r) {
         // two exact multiplications by powers of two: their product alone
         // could leave fp32's range where the result does not
-        v[r] = acc[i][j][r] * inv_a * inv_b;
+        v[r] = MX ? acc[i][j][r] : acc[i][j][r] * inv_a * inv_b;
         if (bias && n + r < N) v[r] += bias[n + r];
         if (relu) v[r] = fmaxf(v[r], 0.f);
       }
@@ -468,10 +662,16 @@ void fp8_quantize(uintptr_t src, bool src_bf16, uintptr_t mask, bool mask_f32,
 static Fp8Operand fp8_operand(uintptr_t p, int64_t red, int64_t rows,
                               uintptr_t scale_ws) {
   return Fp8Operand{(const uint8_t*)p, pad128(red), (int)rows,
-                    (const float*)scale_ws + 1};
+                    (const float*)scale_ws + 1, nullptr};
 }
 
-template <bool A_E5M2>
+static Fp8Operand mx_operand(uintptr_t p, uintptr_t sc, int64_t red,
+                             int64_t rows) {
+  return Fp8Operand{(const uint8_t*)p, pad128(red), (int)rows, nullptr,
+                    (const uint8_t*)sc};
+}
+
+template <bool A_E5M2, bool MX = false>
 static void launch_gemm(const Fp8Operand& a, const Fp8Operand& b, int64_t red,
                         int kchunk, int splits, uintptr_t c, bool out_f32,
                         uintptr_t bias, bool relu, uintptr_t stream) {
@@ -480,13 +680,13 @@ static void launch_gemm(const Fp8Operand& a, const Fp8Operand& b, int64_t red,
     throw std::invalid_argument("linear_fp8: too many output columns");
   const int vec_out = b.rows % 4 == 0;
   if (out_f32)
-    hipLaunchKernelGGL((gemm_fp8_kernel<A_E5M2, float>), grid, dim3(BLK), 0,
-                       S(stream), a, b, (int)pad128(red), kchunk, (float*)c,
-                       (const float*)bias, (int)relu, vec_out);
+    hipLaunchKernelGGL((gemm_fp8_kernel<A_E5M2, MX, float>), grid,
+                       dim3(BLK), 0, S(stream), a, b, (int)pad128(red), kchunk,
+                       (float*)c, (const float*)bias, (int)relu, vec_out);
   else
-    hipLaunchKernelGGL((gemm_fp8_kernel<A_E5M2, bf16_t>), grid, dim3(BLK), 0,
-                       S(stream), a, b, (int)pad128(red), kchunk, (bf16_t*)c,
-                       (const float*)bias, (int)relu, vec_out);
+    hipLaunchKernelGGL((gemm_fp8_kernel<A_E5M2, MX, bf16_t>), grid,
+                       dim3(BLK), 0, S(stream), a, b, (int)pad128(red), kchunk,
+                       (bf16_t*)c, (const float*)bias, (int)relu, vec_out);
 }
 
 // out[B,N] = (xq[B,K] · wq[N,K]ᵀ) / (sx·sw) (+ bias) (ReLU).  sx, sw: the
@@ -546,6 +746,95 @@ void linear_fp8_bwd_w(uintptr_t gyqT, uintptr_t xqT, uintptr_t sg,
   }
 }
 
+// ---------------------------------------------------------------------------
+// K23 — MXFP8 launchers.  Storage as above; a copy's scales are
+// [rows][fp8_pitch(n) / 32] e8m0 bytes.
+// ---------------------------------------------------------------------------
+// Quantise src [R][C] as fp8_quantize does, every 32-block with its own
+// scale: q, sq blocked along C; qT, sqT blocked along R (0 = skip a copy).
+void mxfp8_quantize(uintptr_t src, bool src_bf16, uintptr_t mask,
+                    bool mask_f32, int64_t R, int64_t C, bool e5m2,
+                    uintptr_t q, uintptr_t sq, uintptr_t qT, uintptr_t sqT,
+                    uintptr_t gb_part, uintptr_t gb, uintptr_t stream) {
+  check_dims("mxfp8_quantize", {R, C});
+  if (!src || (!q && !qT) || !q != !sq || !qT != !sqT)
+    throw std::invalid_argument("mxfp8_quantize: null source, no copy asked "
+                                "for, or a copy without its scales");
+  if (gb && !gb_part)
+    throw std::invalid_argument("mxfp8_quantize: gb needs its workspace");
+  check_aligned("mxfp8_quantize", {q, sq, qT, sqT, gb_part});
+  const int64_t row_tiles = qT ? pad128(R) / QT : cdiv((int)R, QT);
+  const int64_t col_tiles = q ? pad128(C) / QT : cdiv((int)C, QT);
+  if (col_tiles > 65535)
+    throw std::invalid_argument("mxfp8_quantize: too many columns");
+  const uintptr_t sb = src_bf16 ? 8 : 16, mb = mask_f32 ? 16 : 8;
+  const int vec = src % sb == 0 && mask % mb == 0 && C % 4 == 0;
+  const dim3 grid((unsigned)row_tiles, (unsigned)col_tiles);
+  by_dtype(src_bf16, [&](auto* t) {
+    using T = elem_t<decltype(t)>;
+    auto quant =
+        e5m2 ? mxfp8_quant_kernel<T, true> : mxfp8_quant_kernel<T, false>;
+    hipLaunchKernelGGL(quant, grid, dim3(BLK), 0, S(stream), (const T*)src,
+                       (const void*)mask, (int)mask_f32, (int)R, (int)C, vec,
+                       (uint8_t*)q, (uint8_t*)sq, pad128(C), (uint8_t*)qT,
+                       (uint8_t*)sqT, pad128(R),
+                       gb ? (float*)gb_part : (float*)nullptr);
+  });
+  if (gb)
+    hipLaunchKernelGGL(gw_combine_kernel, dim3(grid_for(C, BLK)), dim3(BLK), 0,
+                       S(stream), (const float*)gb_part, (float*)gb, C,
+                       (const float*)nullptr, (float*)nullptr, 0,
+                       (int)row_tiles);
+}
+
+// out[B,N] = sum over K blocks of (xq · wqᵀ) 2^(sx-127) 2^(sw-127) (+ bias)
+// (ReLU); sx [B][pitch(K)/32], sw [N][pitch(K)/32]
+void linear_mxfp8_fwd(uintptr_t xq, uintptr_t wq, uintptr_t sx, uintptr_t sw,
+                      uintptr_t bias, uintptr_t out, int64_t B, int64_t K,
+                      int64_t N, bool relu, bool out_f32, uintptr_t stream) {
+  check_dims("linear_mxfp8_fwd", {B, K, N});
+  check_aligned("linear_mxfp8_fwd", {xq, wq, sx, sw, out});
+  launch_gemm<false, true>(mx_operand(xq, sx, K, B), mx_operand(wq, sw, K, N),
+                           K, (int)pad128(K), 1, out, out_f32, bias, relu,
+                           stream);
+}
+
+// gx[B,K] from gyq[B,N] (e5m2) and wqT[K,N], both blocked along N
+void linear_mxfp8_bwd_x(uintptr_t gyq, uintptr_t wqT, uintptr_t sg,
+                        uintptr_t swT, uintptr_t gx, int64_t B, int64_t K,
+                        int64_t N, bool out_f32, uintptr_t stream) {
+  check_dims("linear_mxfp8_bwd_x", {B, K, N});
+  check_aligned("linear_mxfp8_bwd_x", {gyq, wqT, sg, swT, gx});
+  launch_gemm<true, true>(mx_operand(gyq, sg, N, B),
+                          mx_operand(wqT, swT, N, K), N, (int)pad128(N), 1, gx,
+                          out_f32, 0, false, stream);
+}
+
+// gw[N,K] (fp32) from gyqT[N,B] (e5m2) and xqT[K,B], both blocked along B;
+// splits and part as linear_fp8_bwd_w.  A split's chunk is a multiple of
+// 128 bytes, so no block straddles two splits.
+void linear_mxfp8_bwd_w(uintptr_t gyqT, uintptr_t xqT, uintptr_t sgT,
+                        uintptr_t sxT, uintptr_t gw, uintptr_t part,
+                        int splits, int64_t B, int64_t K, int64_t N,
+                        uintptr_t stream) {
+  check_dims("linear_mxfp8_bwd_w", {B, K, N});
+  if (splits != linear_fp8_gw_splits(B, K, N))
+    throw std::invalid_argument("linear_mxfp8_bwd_w: wrong split count");
+  if (splits > 1 && !part)
+    throw std::invalid_argument("linear_mxfp8_bwd_w: no workspace");
+  check_aligned("linear_mxfp8_bwd_w", {gyqT, xqT, sgT, sxT, gw, part});
+  const int kchunk = cdiv(cdiv((int)pad128(B), splits), TK) * TK;
+  launch_gemm<true, true>(mx_operand(gyqT, sgT, B, N),
+                          mx_operand(xqT, sxT, B, K), B, kchunk, splits,
+                          splits > 1 ? part : gw, true, 0, false, stream);
+  if (splits > 1) {
+    const int64_t n_gw = N * K;
+    hipLaunchKernelGGL(gw_combine_kernel, dim3(grid_for(n_gw, BLK)), dim3(BLK),
+                       0, S(stream), (const float*)part, (float*)gw, n_gw,
+                       (const float*)nullptr, (float*)nullptr, 0, splits);
+  }
+}
+
 }  // namespace
 
 void register_linear_fp8(pybind11::module_& m) {
@@ -556,4 +845,8 @@ void register_linear_fp8(pybind11::module_& m) {
   m.def("linear_fp8_bwd_x", &linear_fp8_bwd_x);
   m.def("linear_fp8_gw_splits", &linear_fp8_gw_splits);
   m.def("linear_fp8_bwd_w", &linear_fp8_bwd_w);
+  m.def("mxfp8_quantize", &mxfp8_quantize);
+  m.def("linear_mxfp8_fwd", &linear_mxfp8_fwd);
+  m.def("linear_mxfp8_bwd_x", &linear_mxfp8_bwd_x);
+  m.def("linear_mxfp8_bwd_w", &linear_mxfp8_bwd_w);
 }

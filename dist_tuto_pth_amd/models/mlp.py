@@ -32,18 +32,28 @@ class MLP(nn.Module):
     `ops.linear_fp8`: operands quantised to fp8 per tensor on the 128-deep
     matrix instruction, bf16 hidden activations and dropout, fp32 logits,
     fp32 parameters and gradients under the same names, so a ``state_dict``
-    moves between all three modes."""
+    moves between all three modes.  ``fp8_scaling="mx"`` (fp8 mode only)
+    runs it with MXFP8 block scaling, ``ops.linear_fp8(scaling="mx")``: one
+    e8m0 scale per 32 elements instead of one per tensor."""
 
     def __init__(self, widths: Sequence[int] = (784, 256, 128, 10),
                  dropout: float = 0.2,
-                 compute_dtype: Optional[torch.dtype] = None):
+                 compute_dtype: Optional[torch.dtype] = None,
+                 fp8_scaling: str = "tensor"):
         super().__init__()
         assert len(widths) >= 2
         if compute_dtype not in (None, torch.bfloat16, torch.float8_e4m3fn):
             raise ValueError(
                 f"MLP: compute_dtype must be None, torch.bfloat16 or "
                 f"torch.float8_e4m3fn, got {compute_dtype}")
+        if fp8_scaling not in ("tensor", "mx"):
+            raise ValueError(f"MLP: fp8_scaling must be 'tensor' or 'mx', "
+                             f"got {fp8_scaling!r}")
+        if fp8_scaling != "tensor" and compute_dtype != torch.float8_e4m3fn:
+            raise ValueError("MLP: fp8_scaling needs "
+                             "compute_dtype=torch.float8_e4m3fn")
         self.compute_dtype = compute_dtype
+        self.fp8_scaling = fp8_scaling
         self.widths = list(widths)
         self.p = dropout
         self.layers = nn.ModuleList(
@@ -53,13 +63,14 @@ class MLP(nn.Module):
         x = x.reshape(x.shape[0], self.widths[0])
         for i, lin in enumerate(self.layers):
             last = i == len(self.layers) - 1
-            if self.compute_dtype is not None:
-                lin_op = ops.linear_bf16 \
-                    if self.compute_dtype == torch.bfloat16 \
-                    else ops.linear_fp8
-                x = lin_op(
-                    x, lin.weight, lin.bias, fuse_relu=not last,
-                    out_dtype=torch.float32 if last else torch.bfloat16)
+            out_dtype = torch.float32 if last else torch.bfloat16
+            if self.compute_dtype == torch.bfloat16:
+                x = ops.linear_bf16(x, lin.weight, lin.bias,
+                                    fuse_relu=not last, out_dtype=out_dtype)
+            elif self.compute_dtype is not None:
+                x = ops.linear_fp8(x, lin.weight, lin.bias,
+                                   fuse_relu=not last, out_dtype=out_dtype,
+                                   scaling=self.fp8_scaling)
             else:
                 x = ops.linear(x, lin.weight, lin.bias, fuse_relu=not last)
             if not last:

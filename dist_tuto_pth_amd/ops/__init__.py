@@ -3,7 +3,7 @@
 Every op the reference's ``Net.forward`` + SGD step trigger implicitly
 through torch (train_dist.py:58-71,110,118-124) is a hand-written CDNA4
 HIP kernel here, with forward *and* backward (``csrc/kernels.hip``; K3-K6
-in ``csrc/pointwise.hip``, K16-K22 in the files named at their sections):
+in ``csrc/pointwise.hip``, K16-K23 in the files named at their sections):
 
   K1/K2  conv2d (direct, LDS-tiled)        -> conv2d
   K3+K4  maxpool2d(k2) fused with ReLU     -> maxpool2d_relu (fp32, bf16)
@@ -13,6 +13,9 @@ in ``csrc/pointwise.hip``, K16-K22 in the files named at their sections):
   K7/K8  linear (+fused ReLU epilogue)     -> linear
   K16    bf16 MFMA linear, fp32 accumulate  -> linear_bf16
   K22    fp8 (e4m3/e5m2) 128-deep MFMA linear -> linear_fp8, quantize_fp8
+  K23    MXFP8: e8m0 scales per 32 elements, applied by the scaled MFMA
+                                    -> linear_fp8(scaling="mx"),
+                                       quantize_fp8(block=32)
   K17    bf16 MFMA conv2d (stride, padding) -> conv2d_bf16
          the same on channels-last storage  -> conv2d_bf16(memory_format=
                                               torch.channels_last)
@@ -651,10 +654,75 @@ def _fp8_quantize_gpu(t, dtype, mask=None, want_q=True, want_qT=False,
     return q, qT, ws, gb
 
 
-def quantize_fp8(t, dtype):
+def _mxfp8_quantize_cpu(t, dtype):
+    """``quantize_fp8(block=32)``'s rule with torch ops: the executable
+    statement of the MX contract.  Returns ``(q, scales)``: ``t``'s shape in
+    ``dtype`` and the uint8 e8m0 bytes ``127 - k`` per 32-block of the last
+    dimension."""
+    C = t.shape[-1]
+    nb = -(-C // 32)
+    blocks = F.pad(t.detach().float(), (0, nb * 32 - C)).reshape(
+        t.shape[:-1] + (nb, 32))
+    amax = blocks.abs().amax(-1)
+    m, ex = torch.frexp(amax)            # amax = m * 2^ex, m in [0.5, 1)
+    k = _FP8_E[dtype] - (ex - 1) - (m > 0.875).to(ex.dtype)
+    k = torch.where(amax == 0, torch.zeros_like(k), k.clamp(-126, 126))
+    s = torch.ldexp(torch.ones((), dtype=torch.float32), k)
+    q = (blocks * s.unsqueeze(-1)).to(dtype).reshape(
+        t.shape[:-1] + (nb * 32,))[..., :C]
+    return q, (127 - k).to(torch.uint8)
+
+
+def _mxfp8_dequantize(q, scales):
+    """fp32 ``q * 2^(scales - 127)`` per 32-block of the last dimension
+    (exact: a power-of-two multiple of an fp8 value)."""
+    f = torch.ldexp(torch.ones((), dtype=torch.float32),
+                    scales.to(torch.int32) - 127)
+    return q.float() * f.repeat_interleave(32, -1)[..., :q.shape[-1]]
+
+
+def _mxfp8_quantize_gpu(t, dtype, mask=None, want_q=True, want_qT=False,
+                        want_gb=False):
+    """One launch of K23's quantiser on the dense 2-D CUDA tensor ``t``,
+    zeroed where ``mask <= 0``.  Returns ``(q, sq, qT, sqT, gb)``: the padded
+    uint8 storage blocked along columns with its e8m0 scales, the transposed
+    storage blocked along rows with its scales (None where not wanted), and
+    the fp32 column sums of the masked ``t``."""
+    k = _k()
+    R, C = t.shape
+    dev = t.device
+    q = sq = qT = sqT = gb = gb_part = None
+    if want_q:
+        q = torch.empty(R, k.fp8_pitch(C), device=dev, dtype=torch.uint8)
+        sq = torch.empty(R, k.fp8_pitch(C) // 32, device=dev,
+                         dtype=torch.uint8)
+    if want_qT:
+        qT = torch.empty(C, k.fp8_pitch(R), device=dev, dtype=torch.uint8)
+        sqT = torch.empty(C, k.fp8_pitch(R) // 32, device=dev,
+                          dtype=torch.uint8)
+    if want_gb:
+        gb = torch.empty(C, device=dev, dtype=torch.float32)
+        gb_part = torch.empty(k.fp8_pitch(R) // 64 * C, device=dev,
+                              dtype=torch.float32)
+    k.mxfp8_quantize(t.data_ptr(), t.dtype == torch.bfloat16, _ptr(mask),
+                     mask is not None and mask.dtype == torch.float32, R, C,
+                     dtype == torch.float8_e5m2, _ptr(q), _ptr(sq), _ptr(qT),
+                     _ptr(sqT), _ptr(gb_part), _ptr(gb), _stream())
+    return q, sq, qT, sqT, gb
+
+
+def quantize_fp8(t, dtype, block=None):
     """Quantise ``t`` (fp32 or bf16, at least 1-D, no empty dimension) to
     ``dtype`` (``torch.float8_e4m3fn`` or ``torch.float8_e5m2``) with one
     power-of-two scale for the whole tensor.  Returns ``(q, scale)``.
+
+    ``block=32`` (K23, MXFP8) scales every 32 consecutive elements of the
+    last dimension on their own, the last block of a row completed with
+    zeros, by the rule below applied to the block's amax.  It returns
+    ``(q, scales)`` with ``scales`` the uint8 e8m0 bytes ``127 - k`` of the
+    decode factors ``2^-k``, shape ``t.shape[:-1] + (ceil(C/32),)``, always
+    in [1, 253]; an all-zero block has 127.  On GPU both are views of the
+    kernel's padded storage.  Any other ``block`` raises ``ValueError``.
 
     With ``amax = max|t| = f * 2^e``, ``f`` in [1, 2), the scale is
     ``2^k``, ``k = E - e`` for ``f <= 1.75`` and ``E - 1 - e`` otherwise
@@ -674,11 +742,20 @@ def quantize_fp8(t, dtype):
     if t.dim() < 1 or min(t.shape) < 1:
         raise ValueError(f"quantize_fp8: t must have at least one dimension "
                          f"and none empty, got {tuple(t.shape)}")
+    if block not in (None, 32):
+        raise ValueError(f"quantize_fp8: block must be None or 32, "
+                         f"got {block!r}")
     if not t.is_cuda:
-        return _fp8_quantize_cpu(t, dtype)
-    t2 = t.detach().contiguous().view(-1, t.shape[-1])
+        return _mxfp8_quantize_cpu(t, dtype) if block \
+            else _fp8_quantize_cpu(t, dtype)
+    C = t.shape[-1]
+    t2 = t.detach().contiguous().view(-1, C)
+    if block:
+        q, sq, _, _, _ = _mxfp8_quantize_gpu(t2, dtype)
+        return (q[:, :C].view(dtype).reshape(t.shape),
+                sq[:, :-(-C // 32)].reshape(t.shape[:-1] + (-(-C // 32),)))
     q, _, ws, _ = _fp8_quantize_gpu(t2, dtype)
-    return q[:, :t.shape[-1]].view(dtype).reshape(t.shape), ws[0]
+    return q[:, :C].view(dtype).reshape(t.shape), ws[0]
 
 
 class _LinearFp8(torch.autograd.Function):
@@ -766,7 +843,105 @@ class _LinearFp8(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
-def linear_fp8(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
+# ---------------------------------------------------------------------------
+# K23 — MXFP8: the same three products with one e8m0 scale per 32 elements
+# along each product's reduction axis, applied by the matrix instruction
+# (csrc/linear_fp8.hip).  Forward blocks x and w along K, gx blocks gy and w
+# along N, gw blocks gy and x along B, so a transposed copy is quantised on
+# its own.  No per-tensor scale is left: the fp32 accumulator is the result.
+# ---------------------------------------------------------------------------
+class _LinearMxFp8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, fuse_relu, out_dtype):
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        B, K = x.shape
+        N = w.shape[0]
+        e4m3 = torch.float8_e4m3fn
+        if x.is_cuda:
+            k = _k()
+            # one launch per operand: the copy the backward needs, blocked
+            # along the other axis, comes out of the same tile
+            xq, sx, xqT, sxT, _ = _mxfp8_quantize_gpu(
+                x.detach().contiguous(), e4m3, want_qT=need_w)
+            wq, sw, wqT, swT, _ = _mxfp8_quantize_gpu(
+                w.detach().contiguous(), e4m3, want_qT=need_x)
+            out = torch.empty(B, N, device=x.device, dtype=out_dtype)
+            k.linear_mxfp8_fwd(xq.data_ptr(), wq.data_ptr(), sx.data_ptr(),
+                               sw.data_ptr(), _ptr(b), out.data_ptr(), B, K,
+                               N, fuse_relu, out_dtype == torch.float32,
+                               _stream())
+            ctx.save_for_backward(xqT, sxT, wqT, swT,
+                                  out if fuse_relu else None)
+        else:
+            xd, wd = x.detach(), w.detach()
+            acc = _mxfp8_dequantize(*_mxfp8_quantize_cpu(xd, e4m3)) \
+                @ _mxfp8_dequantize(*_mxfp8_quantize_cpu(wd, e4m3)).t()
+            if b is not None:
+                acc = acc + b
+            if fuse_relu:
+                acc = F.relu(acc)
+            out = acc.to(out_dtype)
+            # dequantised [K,B] and [K,N] copies, blocked along B and N
+            xT = _mxfp8_dequantize(*_mxfp8_quantize_cpu(xd.t(), e4m3)) \
+                if need_w else None
+            wT = _mxfp8_dequantize(*_mxfp8_quantize_cpu(wd.t(), e4m3)) \
+                if need_x else None
+            ctx.save_for_backward(xT, None, wT, None,
+                                  out if fuse_relu else None)
+        ctx.dims = (B, K, N)
+        ctx.x_dtype, ctx.w_dtype = x.dtype, w.dtype
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        xT, sxT, wT, swT, out = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        B, K, N = ctx.dims
+        e5m2 = torch.float8_e5m2
+        gx = gw = gb = None
+        if gy.is_cuda:
+            k = _k()
+            dev = gy.device
+            gq, sg, gqT, sgT, gb = _mxfp8_quantize_gpu(
+                gy.contiguous(), e5m2, mask=out, want_q=need_x,
+                want_qT=need_w or not need_x, want_gb=need_b)
+            if need_x:
+                gx = torch.empty(B, K, device=dev, dtype=ctx.x_dtype)
+                k.linear_mxfp8_bwd_x(gq.data_ptr(), wT.data_ptr(),
+                                     sg.data_ptr(), swT.data_ptr(),
+                                     gx.data_ptr(), B, K, N,
+                                     ctx.x_dtype == torch.float32, _stream())
+            if need_w:
+                gw = torch.empty(N, K, device=dev, dtype=torch.float32)
+                splits = k.linear_fp8_gw_splits(B, K, N)
+                part = torch.empty(splits * N * K, device=dev,
+                                   dtype=torch.float32) \
+                    if splits > 1 else None
+                k.linear_mxfp8_bwd_w(gqT.data_ptr(), xT.data_ptr(),
+                                     sgT.data_ptr(), sxT.data_ptr(),
+                                     gw.data_ptr(), _ptr(part), splits,
+                                     B, K, N, _stream())
+                if ctx.w_dtype == torch.bfloat16:
+                    gw = _to_bf16(gw)
+            return gx, gw, gb, None, None
+        g = gy.float()
+        if out is not None:
+            g = torch.where(out > 0, g, torch.zeros_like(g))
+        if need_x:
+            gd = _mxfp8_dequantize(*_mxfp8_quantize_cpu(g, e5m2))
+            gx = (gd @ wT.t()).to(ctx.x_dtype)
+        if need_w:
+            gdT = _mxfp8_dequantize(*_mxfp8_quantize_cpu(g.t(), e5m2))
+            gw = (gdT @ xT.t()).to(ctx.w_dtype)
+        if need_b:
+            gb = g.sum(0)
+        return gx, gw, gb, None, None
+
+
+def linear_fp8(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16,
+               scaling="tensor"):
     """``relu?(x @ w.T + b)`` with fp8 operands and fp32 accumulation.
 
     ``x`` [B,K] and ``w`` [N,K] are fp32 or bf16, ``b`` is fp32 or None;
@@ -786,7 +961,21 @@ def linear_fp8(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
     (master) weight or rounded once to bf16 for a bf16 weight, and ``gb``
     in fp32 — the column sum of the masked, *unquantised* gradient.  ``gw``
     and ``gb`` are bitwise reproducible.  CPU tensors run the same contract
-    with torch's float8 casts and an fp32 matmul."""
+    with torch's float8 casts and an fp32 matmul.
+
+    ``scaling="mx"`` (K23, MXFP8) gives every 32 consecutive elements along
+    a product's reduction axis their own power-of-two scale
+    (``quantize_fp8(block=32)``'s rule): forward blocks ``x`` and ``w`` along
+    K, ``gx`` blocks the gradient and ``w`` along N, ``gw`` blocks the
+    gradient and ``x`` along B, so each operand is quantised once per axis
+    it is reduced over, in one launch with no amax pass.  The matrix
+    instruction applies the two e8m0 block scales to each block's products;
+    the fp32 accumulator is the result, bias, ReLU and the one rounding
+    follow as above, and ``gw`` and ``gb`` stay bitwise reproducible.  On
+    CPU the operands are dequantised per block and multiplied in fp32."""
+    if scaling not in ("tensor", "mx"):
+        raise ValueError(f"linear_fp8: scaling must be 'tensor' or 'mx', "
+                         f"got {scaling!r}")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"linear_fp8: out_dtype must be torch.bfloat16 or "
                         f"torch.float32, got {out_dtype}")
@@ -807,7 +996,8 @@ def linear_fp8(x, w, b=None, fuse_relu=False, out_dtype=torch.bfloat16):
         if b.shape != (w.shape[0],):
             raise ValueError("linear_fp8: b must have shape [N]")
         b = b.contiguous()
-    return _LinearFp8.apply(x, w, b, bool(fuse_relu), out_dtype)
+    fn = _LinearMxFp8 if scaling == "mx" else _LinearFp8
+    return fn.apply(x, w, b, bool(fuse_relu), out_dtype)
 
 
 # ---------------------------------------------------------------------------
