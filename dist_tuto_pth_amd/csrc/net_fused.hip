@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace py = pybind11;
@@ -678,7 +679,6 @@ net_fused_fwd_tiled_kernel(
   const int half = SPLIT ? (blockIdx.x & 1) : 0;
   const int k0 = half * KL;
   const bool head = gl != nullptr;
-  const float sc = head ? gl[0] / B : 0.f;
   // a pointer made opaque by an empty asm (below) is global by cast: the
   // compiler no longer knows, and flat loads would count against the LDS
   // waits as well
@@ -690,28 +690,58 @@ net_fused_fwd_tiled_kernel(
   // the weights are staged once per workgroup: w1 as [c][28], w2 as
   // [cc][k][g][28] for channel c = CPG*g + cc, so that consecutive
   // conv2 lanes (g fastest, then k) read consecutive 28-float slots
-  for (int i = tid; i < N_C1K * 25; i += FT_NT) {
-    const int c = i / 25, j = i - c * 25;
-    w1p[c * FT_WS + j] = w1[i];
+  // Every load of the prologue is issued before the first wait, the
+  // first sample's x and target in front, so that conv1 starts one memory
+  // round trip after the kernel does; the LDS writes follow.  Dword loads
+  // of the weights: they have no alignment beyond a float's.
+  const int b_first = SPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
+  float4 x_v = make_float4(0.f, 0.f, 0.f, 0.f);
+  int t_first = 0;
+  if (b_first < B) {
+    if (tid < 196)
+      x_v = reinterpret_cast<const float4*>(x + (int64_t)b_first * 784)[tid];
+    t_first = (int)tgt[b_first];
   }
-  for (int i = tid; i < KL * N_C1K * 25; i += FT_NT) {
-    const int kc = i / 25, j = i - kc * 25;
-    const int kl = kc / N_C1K, c = kc - kl * N_C1K;
-    const int slot = ((c % CPG) * KL + kl) * NG + c / CPG;
-    w2p[slot * FT_WS + j] = w2[k0 * 250 + i];
+  const float gl_v = head ? gl[0] : 0.f;
+  {
+    static_assert(N_C1K * 25 <= FT_NT, "w1 in one load per lane");
+    constexpr int N2 = KL * N_C1K * 25;
+    constexpr int NL2 = (N2 + FT_NT - 1) / FT_NT;
+    float w1v = 0.f, w2v[NL2], b1v = 0.f, b2v = 0.f;
+    if (tid < N_C1K * 25) w1v = w1[tid];
+    #pragma unroll
+    for (int t = 0; t < NL2; ++t) {
+      const int i = tid + t * FT_NT;
+      w2v[t] = 0.f;
+      if (t + 1 < NL2 || i < N2) w2v[t] = w2[k0 * 250 + i];
+    }
+    if (tid < N_C1K) b1v = b1[tid];
+    if (tid < KL) b2v = b2[k0 + tid];
+    if (tid < N_C1K * 25) w1p[(tid / 25) * FT_WS + tid % 25] = w1v;
+    #pragma unroll
+    for (int t = 0; t < NL2; ++t) {
+      const int i = tid + t * FT_NT;
+      const int kc = i / 25, j = i - kc * 25;
+      const int kl = kc / N_C1K, c = kc - kl * N_C1K;
+      const int slot = ((c % CPG) * KL + kl) * NG + c / CPG;
+      if (t + 1 < NL2 || i < N2) w2p[slot * FT_WS + j] = w2v[t];
+    }
+    if (tid < N_C1K) b1s[tid] = b1v;
+    if (tid < KL) b2s[tid] = b2v;
   }
-  if (tid < N_C1K) b1s[tid] = b1[tid];
-  if (tid < KL) b2s[tid] = b2[k0 + tid];
+  const float sc = gl_v / B;
 
   float lsum = 0.f;
-  for (int b = SPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x; b < B;
-       b += SPLIT ? B : (int)gridDim.x) {
-    if (tid < 196)
-      reinterpret_cast<float4*>(xs)[tid] =
-          reinterpret_cast<const float4*>(x + (int64_t)b * 784)[tid];
-    // (read here so that neither the softmax lane nor the head's
-    // g_logits waits for it behind a barrier)
-    const int t_b = (int)tgt[b];
+  for (int b = b_first; b < B; b += SPLIT ? B : (int)gridDim.x) {
+    // (the target is read here so that neither the softmax lane nor the
+    // head's g_logits waits for it behind a barrier)
+    int t_b = t_first;
+    if (b != b_first) {
+      if (tid < 196)
+        x_v = reinterpret_cast<const float4*>(x + (int64_t)b * 784)[tid];
+      t_b = (int)tgt[b];
+    }
+    if (tid < 196) reinterpret_cast<float4*>(xs)[tid] = x_v;
     __syncthreads();
     STAGE_STAMP(10);
 
@@ -1421,6 +1451,55 @@ static_assert(BT_RS % 4 == 0 && BT_PS % 4 == 0 && BT_WS % 4 == 0 &&
     w2, wf1, wf2, tgt, gl, idx1_ws, m2_ws, idx2_ws, h1_ws, m3_ws, logp_ws, \
     glog_ws, gh1_ws, ga2_ws, ga1_ws, B, training, split
 
+// The prologue's w2 staging for CGS channel groups (1: all ten channels,
+// 2: the five from c0): NL loads per lane, all issued before the first
+// wait, so the prologue is one memory round trip.  Element i of this
+// sibling's [k][cl][25] goes to w2p[(i / 25) * BT_WS + i % 25]; per k the
+// sibling's channels are one run of w2, so the source is i plus whole k
+// rows.  Dword loads: w2 has no alignment beyond a float's.
+template <int CGS>
+struct BtW2Stage {
+  static constexpr int N = N_C2K * (N_C1K / CGS) * 25;  // elements
+  static constexpr int NL = (N + BT_NT - 1) / BT_NT;    // loads per lane
+  static constexpr int RUN = (N_C1K / CGS) * 25;        // per k
+  float v[NL];
+  __device__ __forceinline__ void load(const float* __restrict__ w2, int c0,
+                                       int tid) {
+    #pragma unroll
+    for (int t = 0; t < NL; ++t) {
+      const int i = tid + t * BT_NT;
+      const int src = CGS == 1 ? i : i + (i / RUN) * (N_C1K * 25 - RUN) +
+                                         c0 * 25;
+      v[t] = 0.f;
+      if (t + 1 < NL || i < N) v[t] = w2[src];
+    }
+  }
+  __device__ __forceinline__ void store(float* w2p, int tid) const {
+    #pragma unroll
+    for (int t = 0; t < NL; ++t) {
+      const int i = tid + t * BT_NT;
+      if (t + 1 < NL || i < N) w2p[(i / 25) * BT_WS + i % 25] = v[t];
+    }
+  }
+};
+
+// The tile's ring: everything outside rows and columns 4..11 of a plane
+// (and the plane's 12 pad floats); no sample writes it.  In float4 terms
+// a plane is 83 quads, a row 5, and the interior is quads 1 and 2 of rows
+// 4..11, so the ring is whole quads.
+__device__ __forceinline__ void bt_zero_ring(float* gd2p, int tid) {
+  static_assert(BT_RS == 20 && BT_PS == 332, "ring enumeration");
+  constexpr int NQ = N_C2K * (BT_PS / 4);
+  #pragma unroll
+  for (int t = 0; t < (NQ + BT_NT - 1) / BT_NT; ++t) {
+    const int i = tid + t * BT_NT;
+    const int q = i % (BT_PS / 4), row = q / 5, col = q - row * 5;
+    const bool inner = row >= 4 && row <= 11 && (col == 1 || col == 2);
+    if (i < NQ && !inner)
+      reinterpret_cast<float4*>(gd2p)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
 template <bool HEAD>
 __device__ __forceinline__ void net_bwd_tiled_body(
     BT_KERNEL_PARAMS,
@@ -1431,12 +1510,17 @@ __device__ __forceinline__ void net_bwd_tiled_body(
 
   // the grid is B * split or a multiple of 8 (host), so a workgroup
   // keeps one sibling index over its grid-stride loop
-  const int half = blockIdx.x % split;
-  const int cgs = split >= 2 ? 2 : 1, prs = split / cgs;
-  const int nc = N_C1K / cgs, c0 = (half / prs) * nc;
-  const int p0 = 18 * (half % prs) / prs;
-  const int p1 = 18 * (half % prs + 1) / prs;
-  const int ppr = BT_ROUND / nc;  // positions per round
+  // (split is 1, 2, 4 or 8 (host): shifts and masks, no run-time division
+  // ahead of the staging)
+  const int lsp = __builtin_ctz(split);
+  const int half = blockIdx.x & (split - 1);
+  const int cgs = split >= 2 ? 2 : 1, lpr = split >= 2 ? lsp - 1 : 0;
+  const int prs = 1 << lpr;
+  const int nc = cgs == 2 ? N_C1K / 2 : N_C1K, c0 = (half >> lpr) * nc;
+  const int p0 = (18 * (half & (prs - 1))) >> lpr;
+  const int p1 = (18 * ((half & (prs - 1)) + 1)) >> lpr;
+  // positions per round
+  const int ppr = cgs == 2 ? BT_ROUND / (N_C1K / 2) : BT_ROUND / N_C1K;
 
   STAGE_STAMP(0);
   // !HEAD: lane t < 320 moves float4 t of ga2_ws[b], the half-row
@@ -1447,25 +1531,28 @@ __device__ __forceinline__ void net_bwd_tiled_body(
   float4 t_v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (!HEAD && tid < N_A2 / 4 && (int)blockIdx.x < B * split)
     t_v = reinterpret_cast<const float4*>(
-        ga2_ws + (int64_t)(blockIdx.x / split) * N_A2)[tid];
-  for (int i = tid; i < N_C2K * nc * 25; i += BT_NT) {
-    const int kc = i / 25, j = i - kc * 25;
-    const int k = kc / nc, cl = kc - k * nc;
-    w2p[kc * BT_WS + j] = w2[(k * N_C1K + c0 + cl) * 25 + j];
-  }
+        ga2_ws + (int64_t)(blockIdx.x >> lsp) * N_A2)[tid];
+  // every load of the prologue is issued before the first wait: the ga2
+  // float4 above, this sibling's w2 elements and the loss gradient; the
+  // ring is zeroed while they are in flight
   float sc = 0.f;
-  if (HEAD) sc = gl[0] / B;
-  if (!HEAD) {
-    // the tile's ring: everything outside rows and columns 4..11 of a
-    // plane (and the plane's 12 pad floats); no sample writes it
-    for (int i = tid; i < N_C2K * BT_PS; i += BT_NT) {
-      const int r = i % BT_PS, row = r / BT_RS, col = r - row * BT_RS;
-      if (row < 4 || row > 11 || col < 4 || col > 11) gd2p[i] = 0.f;
-    }
+  if (cgs == 2) {
+    BtW2Stage<2> st;
+    st.load(w2, c0, tid);
+    if (HEAD) sc = gl[0];
+    if (!HEAD) bt_zero_ring(gd2p, tid);
+    st.store(w2p, tid);
+  } else {
+    BtW2Stage<1> st;
+    st.load(w2, 0, tid);
+    if (HEAD) sc = gl[0];
+    if (!HEAD) bt_zero_ring(gd2p, tid);
+    st.store(w2p, tid);
   }
+  if (HEAD) sc = sc / B;
 
   for (int bb = blockIdx.x; bb < B * split; bb += gridDim.x) {
-    const int b = bb / split;
+    const int b = bb >> lsp;
     if (HEAD) {
       // (its leading barrier also orders the w2p staging and the previous
       // sample's last tile reads)
@@ -1492,6 +1579,23 @@ __device__ __forceinline__ void net_bwd_tiled_body(
 
     for (int pb = p0; pb < p1; pb += ppr) {
       const int nt = min(ppr, p1 - pb) * nc;  // tiles this round
+      // the round's pool1 index bytes, at most two per lane, are loaded
+      // here: their addresses do not depend on the tiles, and the FMAs
+      // cover the round trip
+      static_assert(BT_ROUND * 8 <= 2 * BT_NT, "two outputs per lane");
+      uint8_t iv[2] = {0, 0};
+      #pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int o = tid + it * BT_NT;
+        if (o < nt * 8) {
+          const int tl = o >> 3, j = o & 7;
+          const int pl = tl / nc, c = c0 + tl - pl * nc;
+          const int pos = pb + pl;
+          const int h = (pos / 3) * 2 + (j >> 2);
+          const int wc = (pos % 3) * 4 + (j & 3);
+          iv[it] = idx1_ws[(int64_t)b * N_P1 + c * 144 + h * 12 + wc];
+        }
+      }
       if (tid < nt * BT_KG) {
         const int kg = tid / nt, tl = tid - kg * nt;
         const int pl = tl / nc, cl = tl - pl * nc;
@@ -1570,7 +1674,10 @@ __device__ __forceinline__ void net_bwd_tiled_body(
       STAGE_STAMP(7);
       // fixed-order sum of the k-group partials, then pool1 bwd: each
       // pooled position owns its 2x2 ga1 window, all four slots written
-      for (int o = tid; o < nt * 8; o += BT_NT) {
+      #pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int o = tid + it * BT_NT;
+        if (o >= nt * 8) break;
         const int tl = o >> 3, j = o & 7;
         float g = part[o];
         #pragma unroll
@@ -1578,7 +1685,7 @@ __device__ __forceinline__ void net_bwd_tiled_body(
         const int pl = tl / nc, c = c0 + tl - pl * nc;
         const int pos = pb + pl;
         const int h = (pos / 3) * 2 + (j >> 2), wc = (pos % 3) * 4 + (j & 3);
-        const uint8_t v = idx1_ws[(int64_t)b * N_P1 + c * 144 + h * 12 + wc];
+        const uint8_t v = iv[it];
         const int am = v & 3;
         if (v & 4) g = 0.f;
         float* gp = ga1_ws + (int64_t)b * N_A1 + c * 576 + h * 2 * 24 +
@@ -1881,6 +1988,54 @@ __device__ __forceinline__ void net_gw_conv1_mfma(
     *(dst + i) = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
 
+// The fc tiles' operands: up to GW_FC_NB samples are loaded before the
+// first FMA (one memory round trip per batch instead of one per sample or
+// pair), then accumulated in the order of the plain loops: sample j of a
+// batch goes to chain `e` when j is even and to `o` when odd (fc1's two
+// chains; fc2 passes one accumulator as both and so keeps sample order).
+// Explicit FMAs: the loops compiled to fused multiply-adds, and written
+// `+=` over preloaded registers they may be split into packed multiplies
+// and adds.  A block's sample count is uniform, hence the switch.
+#define GW_FC_NB 8
+static_assert(GW_FC_NB % 2 == 0, "a batch keeps the even/odd chains");
+template <int NB>
+__device__ __forceinline__ void gw_fc_dot(const float* __restrict__ g,
+                                          int sg,
+                                          const float* __restrict__ p,
+                                          int sp, float& e, float& o) {
+  float gv[NB], pv[NB];
+  #pragma unroll
+  for (int j = 0; j < NB; ++j) { gv[j] = g[j * sg]; pv[j] = p[j * sp]; }
+  #pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    if (j & 1) o = fmaf(gv[j], pv[j], o);
+    else e = fmaf(gv[j], pv[j], e);
+  }
+}
+template <int NB>
+__device__ __forceinline__ void gw_fc_sum(const float* __restrict__ g,
+                                          int sg, float& acc) {
+  float gv[NB];
+  #pragma unroll
+  for (int j = 0; j < NB; ++j) gv[j] = g[j * sg];
+  #pragma unroll
+  for (int j = 0; j < NB; ++j) acc += gv[j];
+}
+template <class F>
+__device__ __forceinline__ void gw_fc_count(int nb, F&& f) {
+  switch (nb) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: break;
+  }
+}
+
 // One (tile, batch-chunk) partial weight-gradient reduction.  Tiles
 // walk [conv2 x8 | conv1 x8 | fc1 | fc2]; partials land in my[GW_ROW]
 // laid out like the flat grad buffer.  Shared by net_gw_partial_kernel
@@ -1921,22 +2076,21 @@ __device__ __forceinline__ void net_gw_tile(
       if (i < 16000) {
         const int n = i / N_P2, k = i % N_P2;
         float ae = 0.f, ao = 0.f;
-        int b = b0;
-        for (; b + 1 < b1; b += 2) {
-          ae += gh1_ws[(int64_t)b * N_H1 + n] *
-                p2_ws[(int64_t)b * N_P2 + k];
-          ao += gh1_ws[(int64_t)(b + 1) * N_H1 + n] *
-                p2_ws[(int64_t)(b + 1) * N_P2 + k];
-        }
-        if (b < b1)
-          ae += gh1_ws[(int64_t)b * N_H1 + n] *
-                p2_ws[(int64_t)b * N_P2 + k];
+        for (int b = b0; b < b1; b += GW_FC_NB)
+          gw_fc_count(min(GW_FC_NB, b1 - b), [&](auto nb) {
+            gw_fc_dot<decltype(nb)::value>(
+                gh1_ws + (int64_t)b * N_H1 + n, N_H1,
+                p2_ws + (int64_t)b * N_P2 + k, N_P2, ae, ao);
+          });
         acc = ae + ao;
         *(my + OFF_WF1 + i) = acc;
       } else {
         const int n = i - 16000;
-        for (int b = b0; b < b1; ++b)
-          acc += gh1_ws[(int64_t)b * N_H1 + n];
+        for (int b = b0; b < b1; b += GW_FC_NB)
+          gw_fc_count(min(GW_FC_NB, b1 - b), [&](auto nb) {
+            gw_fc_sum<decltype(nb)::value>(gh1_ws + (int64_t)b * N_H1 + n,
+                                           N_H1, acc);
+          });
         *(my + OFF_BF1 + n) = acc;
       }
     }
@@ -1949,14 +2103,20 @@ __device__ __forceinline__ void net_gw_tile(
       float acc = 0.f;
       if (i < 500) {
         const int n = i / N_H1, k = i % N_H1;
-        for (int b = b0; b < b1; ++b)
-          acc += glog_ws[(int64_t)b * N_CLS + n] *
-                 d3_ws[(int64_t)b * N_H1 + k];
+        for (int b = b0; b < b1; b += GW_FC_NB)
+          gw_fc_count(min(GW_FC_NB, b1 - b), [&](auto nb) {
+            gw_fc_dot<decltype(nb)::value>(
+                glog_ws + (int64_t)b * N_CLS + n, N_CLS,
+                d3_ws + (int64_t)b * N_H1 + k, N_H1, acc, acc);
+          });
         *(my + OFF_WF2 + i) = acc;
       } else {
         const int n = i - 500;
-        for (int b = b0; b < b1; ++b)
-          acc += glog_ws[(int64_t)b * N_CLS + n];
+        for (int b = b0; b < b1; b += GW_FC_NB)
+          gw_fc_count(min(GW_FC_NB, b1 - b), [&](auto nb) {
+            gw_fc_sum<decltype(nb)::value>(glog_ws + (int64_t)b * N_CLS + n,
+                                           N_CLS, acc);
+          });
         *(my + OFF_BF2 + n) = acc;
       }
     }
